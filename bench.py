@@ -3,8 +3,14 @@
 path (BASELINE.json configs[1]: nuScenes polar-pillar cfg, synthetic 30k-point sweeps, forward
 only, fp32) on N MI355X GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up (model, resident frames, FramePipeline with its measured stream assignment, chain form and depth), warms up,
+times the K steps and prints the line with the headline objects only.  `--full` adds every secondary measurement below (the
+objects marked [full]); the `--no-*` options switch single ones of them off again.  `--dump-outputs DIR` writes the head tensors
+the last timed step handed back as DIR/<name>.npy (float32).
 
 Launched bare with N > 1 (no RANK / WORLD_SIZE in the environment) the script starts N child
 processes of itself, one per GPU, before anything touches the GPU (the reference launches one
@@ -20,21 +26,25 @@ over ranks is reported.
 
 Objects in the JSON line:
   value / ms_per_step        the timed region: K hipGraph replays, `--streams` frames in flight (default: 3 or 4, measured)
-  single_stream_ms_per_step  the same K replays with ONE frame in flight (latency regime) -- the regime `roofline` is
+  replay_stream_tuning       what FramePipeline measured at construction (stream assignment, chain form, depth)
+  [full] value_sustained / sustained   the same loop over >= 200 steps
+  [full] single_stream_ms_per_step  the same K replays with ONE frame in flight (latency regime) -- the regime `roofline` is
                              quoted in, so roofline.conv_ms_per_step <= single_stream_ms_per_step
-  roofline          the dominant kernel (fp32-MFMA implicit-GEMM convolution): algorithmic FLOPs of every launch / its
+  [full] summary / summary_tail / config.secondary   the secondary figures in one flat object and one short string
+  [full] batched    the same frames at the reference config's batch of 4 sweeps per replay
+  [full] roofline   the dominant kernel (fp32-MFMA implicit-GEMM convolution): algorithmic FLOPs of every launch / its
                     own execution time (events attached to the dispatch, = rocprofv3's kernel duration), one stream
-  roofline_scatter  the scatter stage V0..V5 against the HBM roofline: algorithmic bytes of the variant that is run
+  [full] roofline_scatter  the scatter stage V0..V5 against the HBM roofline: algorithmic bytes of the variant that is run
                     (persistent canvas + sparse clear: the dense canvas is never moved) / time of the stage's hipGraph
-  train_step        BASELINE configs[2]: the DDP training iteration at bs = 4 sweeps per GPU (fwd + loss + bwd + bucketed
+  [full] train_step        BASELINE configs[2]: the DDP training iteration at bs = 4 sweeps per GPU (fwd + loss + bwd + bucketed
                     gradient all-reduce overlapped with backward + clip / wd / Adam)
-  cpu_baseline      the CPU oracle (oracle/polar_oracle.py, a port of the reference path checked against reference
+  [full] cpu_baseline      the CPU oracle (oracle/polar_oracle.py, a port of the reference path checked against reference
                     goldens) timed on this box's host cores, rank 0, N=1 only.
-  c4                BASELINE configs[3] (N=1): the Waymo PARTNER detector at bs = 2, f32 and with bf16 BEV convolutions: ms per
+  [full] c4                BASELINE configs[3] (N=1): the Waymo PARTNER detector at bs = 2, f32 and with bf16 BEV convolutions: ms per
                     step, per-stage ms, issued-MFMA roofline fraction per MFMA stage (partner_amd/utils/legs.py)
-  c5                BASELINE configs[4] (N=1): 300k-point streaming frames, one hipGraph replay per frame, latency p50 / p99
-  roofline_scatter_coarse   SURVEY 8(d)'s secondary row: the scatter stage on the 0.3125 m x 0.05 rad synthetic grid
-  ranks             N > 1: what every rank saw (world size after init, device ordinal, PCI bus id, host)
+  [full] c5                BASELINE configs[4] (N=1): 300k-point streaming frames, one hipGraph replay per frame, latency p50 / p99
+  [full] roofline_scatter_coarse   SURVEY 8(d)'s secondary row: the scatter stage on the 0.3125 m x 0.05 rad synthetic grid
+  ranks             what every rank saw (world size after init, device ordinal, PCI bus id, host)
 
 roofline.frac is the matrix work ISSUED (MFMA FLOPs the kernels execute: Winograd launches issue 2/3 resp. 1/2 of the direct
 algorithm's FLOPs) / kernel time / 157.3 TFLOP/s, so it cannot exceed 1; the direct algorithm's FLOPs over the same time are
@@ -427,6 +437,42 @@ def committed_pmc_bytes(kernel_prefixes, per="frame"):
     return round(tot / frames) if per == "frame" else round(tot / n)
 
 
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_BUDGET_BYTES = 63 << 20      # array data; with the .npy headers the files stay under 64 MB
+
+
+def _named_tensors(prefix, obj):
+    if isinstance(obj, torch.Tensor):
+        yield prefix or "out", obj
+    elif isinstance(obj, dict):
+        for k in sorted(obj):
+            yield from _named_tensors(f"{prefix}.{k}" if prefix else str(k), obj[k])
+    elif isinstance(obj, (list, tuple)):
+        for j, v in enumerate(obj):
+            yield from _named_tensors(f"{prefix}.{j}" if prefix else str(j), v)
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every tensor the timed path handed back in its last step as DIR/<name>.npy (float32; float64 and integers as
+    float64).  Within 64 MB in all the arrays are written whole; above that each array is cut to a fixed, seeded sample of its
+    flattened elements (sorted indices, numpy default_rng(0)), sized in proportion to the array."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = []
+    for name, t in _named_tensors("", outputs):
+        t = t.detach()
+        if t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool):
+            arrays.append((name, t.to(torch.float64).cpu().numpy()))
+        else:
+            arrays.append((name, t.to(torch.float32).cpu().numpy()))
+    total = sum(a.nbytes for _, a in arrays)
+    for name, a in arrays:
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.size * DUMP_BUDGET_BYTES // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(keep, a.size), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ------------------------------------------------------------------------------------------------ main
 def rank_table(rank, world, dev_index=None):
     """what every rank saw after the rendezvous: -> (ranks_seen, [per-rank dict]) on every rank.  ranks_seen is
@@ -510,7 +556,15 @@ def main():
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 200-step repeat of the timed loop (`value_sustained`; counter passes of the profiler)")
     ap.add_argument("--no-c4", action="store_true", help="skip the Waymo PARTNER leg (BASELINE configs[3], N = 1 only)")
     ap.add_argument("--no-c5", action="store_true", help="skip the 300k-point streaming leg (BASELINE configs[4], N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="inference mode: after the headline, every secondary measurement (sustained, one frame in flight, batch 4, rooflines, "
+                         "scatter stage, C5, training leg, C4, CPU baseline; the --no-* options above skip single ones); a plain run times the "
+                         "headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="inference mode: write the head tensors of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "infer" or args.dry_run):
+        ap.error("--dump-outputs writes what the inference path computed: --mode infer only, not with --dry-run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)     # before anything touches the GPU
@@ -618,13 +672,16 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        out = step(i)
     barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, red_dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)       # (static buffers of the last step's engine: no later step has run)
+    full = args.full
 
     # the same loop over >= 200 steps (the K timed steps above are 13 ms at the default K = 20: this is the sustained figure beside them)
     sustained = None
-    if engines and not args.no_sustained:
+    if engines and full and not args.no_sustained:
         ks = max(200, 4 * args.steps)
         barrier()
         t1 = time.perf_counter()
@@ -643,7 +700,7 @@ def main():
     # the same K frames with ONE frame in flight (one engine, one stream): the regime the per-kernel figures are quoted in
     # (an engine of its own: the engines above are captured with the hint that several frames are in flight, this one has the chip to itself)
     single_ms = None
-    if engines:
+    if engines and full:
         lat_engine = engines[0] if len(engines) == 1 else FrameEngine(model, B, N, spec).capture()
         for i in range(20):      # (a freshly captured graph: its first replays carry the upload; 20 = 16 ms, untimed)
             lat_engine.run(frames[i % pool], sync=False)
@@ -662,7 +719,7 @@ def main():
     # headline, which stays at one sweep per step like the reference's speed test; per-frame results are identical (eval-mode BatchNorm /
     # per-sample GroupNorm).
     batched = None
-    if engines and B == 1 and not args.no_batched:
+    if engines and B == 1 and full and not args.no_batched:
         from partner_amd.engine import FrameEngine
         GB, GS = 4, min(2, depth)
         groups = [torch.cat([frames[(GB * f + j) % pool] for j in range(GB)], 0) for f in range(max(1, pool // GB))]
@@ -754,7 +811,7 @@ def main():
         return r
 
     roofline = roofline_single = None
-    if not args.no_roofline_events:
+    if full and not args.no_roofline_events:
         k_hint = depth
         roofline = conv_roofline(k_hint, pipe.chain44 if engines else True, full=True)
         if k_hint > 1:
@@ -763,7 +820,7 @@ def main():
 
     # every rank runs the stage measurement (rank 0's is reported): no rank waits in a collective while another measures alone
     scatter = coarse = scatter300 = None
-    if not args.no_roofline_events and B == 1:
+    if full and not args.no_roofline_events and B == 1:
         scatter = scatter_roofline(model, dev, N, spec)
         try:      # the same stage on a C5-sized frame (300k points in one sweep: ~180k pillars; bytes from N and V, no PMC row for this size)
             scatter300 = scatter_roofline(model, dev, 300000, spec)
@@ -778,7 +835,7 @@ def main():
 
     # BASELINE configs[4] and configs[3] on this GPU (N = 1 only: secondary objects of the default line)
     c5 = c4 = None
-    if world == 1 and B == 1 and not args.eager:
+    if full and world == 1 and B == 1 and not args.eager:
         from partner_amd.utils import legs
         if not args.no_c5:
             try:
@@ -792,13 +849,13 @@ def main():
     torch.cuda.synchronize()
     torch.cuda.set_stream(torch.cuda.default_stream(dev))
     train = None
-    if not args.no_train_leg:
+    if full and not args.no_train_leg:
         engines.clear()        # free the graphs' private pools before the training iteration allocates its activations
         torch.cuda.empty_cache()
         train = run_train(args, model, dev, rank, world, red_dev, steps=min(args.steps, 20), warmup=5)
 
     torch.cuda.set_stream(aux_stream)
-    if world == 1 and B == 1 and not args.eager and not args.no_c4:
+    if full and world == 1 and B == 1 and not args.eager and not args.no_c4:
         from partner_amd.utils import legs
         engines.clear()
         torch.cuda.empty_cache()
@@ -861,11 +918,17 @@ def main():
             "replay_stream_tuning": stream_tuning,
             "roofline": roofline, "roofline_single_stream": roofline_single,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(N, B)
-            line["gpu_over_cpu"] = round(fps / line["cpu_baseline"]["value"], 1)
-        line.update({"batched": batched, "roofline_scatter": scatter, "roofline_scatter_300k": scatter300, "roofline_scatter_coarse": coarse,
-                     "train_step": train, "c4": c4, "c5": c5, "ranks_seen": ranks_seen, "ranks": ranks, "summary_tail": summary})
+        if not full:      # a plain run measured the headline only: none of the secondary objects
+            for k in ("summary", "value_sustained", "sustained", "single_stream_ms_per_step", "roofline", "roofline_single_stream"):
+                del line[k]
+            del line["config"]["secondary"]
+            line.update({"ranks_seen": ranks_seen, "ranks": ranks})
+        else:
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(N, B)
+                line["gpu_over_cpu"] = round(fps / line["cpu_baseline"]["value"], 1)
+            line.update({"batched": batched, "roofline_scatter": scatter, "roofline_scatter_300k": scatter300, "roofline_scatter_coarse": coarse,
+                         "train_step": train, "c4": c4, "c5": c5, "ranks_seen": ranks_seen, "ranks": ranks, "summary_tail": summary})
         print(json.dumps(line), flush=True)
     if world > 1:
         D.barrier()

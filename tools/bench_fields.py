@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""print a few fields of bench.py's JSON line read from stdin:  python bench.py ... | python tools/bench_fields.py [label]"""
+"""print a few fields of bench.py's JSON line read from stdin:  python bench.py --full ... | python tools/bench_fields.py [label]"""
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d.get("roofline") or {}

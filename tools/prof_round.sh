@@ -21,7 +21,7 @@ timeout 900 rocprofv3 --pmc FETCH_SIZE TCC_HIT_sum --kernel-trace --output-forma
 timeout 900 rocprofv3 --pmc WRITE_SIZE TCC_MISS_sum --kernel-trace --output-format csv -d "$OUT/write" -o w -- python3 $B $PM > /dev/null 2> "$OUT/pmc_write.err"
 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d "$OUT/sq" -o q -- python3 $B $PM > /dev/null 2> "$OUT/pmc_sq.err" || echo "SQ pass failed (see pmc_sq.err)"
 cd "$ROOT"
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 SQ_PMC_DIR="$OUT/sq" python3 tools/summarize_profile.py "$OUT/stats1" "$OUT/fetch" "$OUT/write" "$OUT/bench_default.json" "$OUT/sum/${PFX}"
 python3 - "$OUT" "$PFX" <<'PY'
 import csv, glob, sys
