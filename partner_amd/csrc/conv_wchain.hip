@@ -557,12 +557,86 @@ __device__ __forceinline__ void wchain3_kloop(const WChainArgs& a, const __amdgp
   }
 }
 
+// The same K loop for a wave that holds TWO 32-column sets (64 output channels) of its three height positions: one height-transformed
+// fragment feeds 24 MFMAs instead of 12, so the plane loads and the transform VALU per MFMA halve.  Six accumulators are 96 registers; with
+// three waves per SIMD (168 registers each) the operands are single-buffered: a step's plane rows are dead once B^T d has read them and are
+// refilled at once (a whole step of 24 MFMAs ahead), a column set's weights right after its 12 MFMAs.  The issue order is pinned, so the
+// compiler's counted waits stay exact: d (5), u[0] (3), u[1] (3) in flight while the previous ones are used.  Per accumulator the MFMA
+// sequence is that of wchain3_kloop (same b, same k order): the same bits.
+template <int SH>
+__device__ __forceinline__ void wchain3_kloop2(const WChainArgs& a, const __amdgpu_buffer_rsrc_t rsrc_v, const __amdgpu_buffer_rsrc_t rsrc_w, const int p,
+                                               const unsigned voff, const unsigned uoff, f32x16 (&acc)[2][3]) {
+  const unsigned cp16 = (unsigned)a.cout_pad * 16u;
+  const unsigned row16 = (unsigned)a.Wq * 16u;
+  f32x4 d[5], u[2][3];
+  bool first = false;      // (diagnostic builds only: PN_WCHAIN_EXP)
+  auto load_d = [&](int cg) __attribute__((always_inline)) {
+    const unsigned so_v = (unsigned)((p * a.cg_in + cg) * 2) * a.plane_bytes + (unsigned)SH * row16;
+    if (!(PN_WCHAIN_EXP & 2) || first) {
+#pragma unroll
+      for (int r = 0; r < 5; ++r) d[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_v, voff, so_v + (unsigned)r * row16, 0));
+    }
+  };
+  auto load_u = [&](int cg, int c) __attribute__((always_inline)) {      // column set c: columns 32 c .. 32 c + 31 of the wave's 64
+    const unsigned so_u = (unsigned)((((cg >> 2) * 6 + 3 * SH) * 6 + p) * 8 + (cg & 3) * 2) * cp16 + (unsigned)c * 512u;
+    if (!(PN_WCHAIN_EXP & 4) || first) {
+#pragma unroll
+      for (int s2 = 0; s2 < 3; ++s2) u[c][s2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, uoff, so_u + (unsigned)(s2 * 48) * cp16, 0));
+    }
+  };
+  const int cg_last = a.cg_in - 1;
+  first = true;
+  load_d(0);
+  __builtin_amdgcn_sched_barrier(0);
+  load_u(0, 0);
+  __builtin_amdgcn_sched_barrier(0);
+  load_u(0, 1);
+  __builtin_amdgcn_sched_barrier(0);
+  first = false;
+  for (int cg = 0; cg <= cg_last; ++cg) {
+    const int nx = cg < cg_last ? cg + 1 : cg_last;      // the last refills re-read a live group (stay inside the buffers)
+    f32x4 b[3];
+    const f32x4 c4 = {4.f, 4.f, 4.f, 4.f}, m4 = {-4.f, -4.f, -4.f, -4.f}, m5 = {-5.f, -5.f, -5.f, -5.f}, c2 = {2.f, 2.f, 2.f, 2.f}, m2 = {-2.f, -2.f, -2.f, -2.f};
+    if constexpr (PN_WCHAIN_EXP & 1) {
+      b[0] = d[0]; b[1] = d[1]; b[2] = d[2];
+    } else if constexpr (SH == 0) {      // the expressions of wchain3_kloop
+      const f32x4 e = __builtin_elementwise_fma(m4, d[2], d[4]), o = __builtin_elementwise_fma(m4, d[1], d[3]);
+      b[0] = __builtin_elementwise_fma(c4, d[0], __builtin_elementwise_fma(m5, d[2], d[4]));
+      b[1] = e + o;
+      b[2] = e - o;
+    } else {
+      const f32x4 f = d[3] - d[1], t = d[2] - d[0];
+      b[0] = __builtin_elementwise_fma(c2, t, f);
+      b[1] = __builtin_elementwise_fma(m2, t, f);
+      b[2] = __builtin_elementwise_fma(c4, d[0], __builtin_elementwise_fma(m5, d[2], d[4]));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_d(nx);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int s2 = 0; s2 < 3; ++s2) {
+          if (PN_WC3_EXP & 1) acc[c][s2][0] += u[c][s2][j] * b[s2][j];      // (keeps the operands alive)
+          else acc[c][s2] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[c][s2][j], b[s2][j], acc[c][s2], 0, 0, 0);
+        }
+      __builtin_amdgcn_sched_barrier(0);
+      load_u(nx, c);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
 // QT = 2: rows of 64 quads (the 256-pixel rows).  The join holds ONE 32-quad tile, so the two halves of a row group are computed one after
 // the other; what the finish of one half needs from the other is one pixel per row and channel on either side of the cut -- the next layer's
 // input transform of quad 31 takes the first pixel of quad 32 and vice versa.  Half 0 therefore leaves quad 31's four pixels and quad 30's
 // last one in a 2.5 KB carry instead of storing quad 31's planes; half 1 takes its left neighbour from there and its first lane completes
 // quad 31.  Same values as an undivided row.
-template <int QT>
+// NC = 2: 64 output channels per block (wchain3_kloop2): the block reads its input rows once for 64 channels instead of 32 -- half the blocks
+// re-read the planes -- and the join and finish run once per 32-column set (the join of 64 columns would be 192 KB), with one carry per set.
+template <int QT, int NC>
 __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
   constexpr int NW = 12;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -575,7 +649,7 @@ __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, a.w_bytes, 0x00020000);
   const int Hq = a.H >> 2;
   f32x4* J = reinterpret_cast<f32x4*>(smem);      // [p 6][row 4][g 4][lane 64]
-  f32x4* carry = J + 6 * 4 * 4 * 64;              // QT = 2: [row 4][g 4][lh 2][5]: quad 31's pixels 0 .. 3 and quad 30's pixel 3
+  f32x4* carry = J + 6 * 4 * 4 * 64;              // QT = 2: [set NC][row 4][g 4][lh 2][5]: quad 31's pixels 0 .. 3 and quad 30's pixel 3
   const float lo = a.act == PN_ACT_RELU ? 0.f : -__builtin_inff();
   const int bid = blockIdx.x;
   int qt, ctile;
@@ -587,27 +661,46 @@ __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
     qt = bid / a.ctiles;
     ctile = bid - qt * a.ctiles;
   }
-  const int n0 = ctile * 32;
+  const int n0 = ctile * 32 * NC;
   const int o0 = qt * 32 * QT;          // first hexadecet of the block
   const int rg0 = o0 >> a.wq_log2, img0 = rg0 / Hq, t0 = rg0 - img0 * Hq;      // block-uniform; rows = row groups
   const unsigned uoff = (unsigned)(((size_t)lh * a.cout_pad + n0 + li) * 16);
 #pragma unroll 1
   for (int sub = 0; sub < QT; ++sub) {
-    int img, t, xq;
-    wchain_coords(img0, t0, Hq, a.wq_log2, 32 * sub + li, img, t, xq);
+    // NC = 2: the lane's coordinates are formed again in every half and after the K loop (hoisted or kept across it they no longer fit
+    // the 168 registers beside the six accumulators)
+    int li, lh, img, t, xq;
+    auto lane_coords = [&]() __attribute__((always_inline)) {
+      int ln = lane;
+      if constexpr (NC == 2) asm volatile("" : "+v"(ln));
+      li = ln & 31;
+      lh = ln >> 5;
+      wchain_coords(img0, t0, Hq, a.wq_log2, 32 * sub + li, img, t, xq);
+    };
+    lane_coords();
     // padded row index of image row 4 t - 1 is 4 t
     const unsigned voff = (unsigned)(((img * (a.H + 2) + 4 * t) * a.Wq + xq) * 16) + (unsigned)lh * a.plane_bytes;
-    f32x16 acc[3];
+    f32x16 acc[NC][3];
 #pragma unroll
-    for (int s = 0; s < 3; ++s)
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
-    if (sh == 0) wchain3_kloop<0>(a, rsrc_v, rsrc_w, p, voff, uoff, acc);
-    else wchain3_kloop<1>(a, rsrc_v, rsrc_w, p, voff, uoff, acc);
-    if (PN_WC3_EXP & 2) {      // no join: the accumulators only have to stay alive
-      if (acc[0][0] + acc[1][3] + acc[2][7] == 1234.5f) J[lane] = f32x4{acc[0][1], acc[1][1], acc[2][1], 0.f};
+      for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[c][s][r] = 0.f;
+    if constexpr (NC == 1) {
+      if (sh == 0) wchain3_kloop<0>(a, rsrc_v, rsrc_w, p, voff, uoff, acc[0]);
+      else wchain3_kloop<1>(a, rsrc_v, rsrc_w, p, voff, uoff, acc[0]);
+    } else {
+      if (sh == 0) wchain3_kloop2<0>(a, rsrc_v, rsrc_w, p, voff, uoff, acc);
+      else wchain3_kloop2<1>(a, rsrc_v, rsrc_w, p, voff, uoff, acc);
+      lane_coords();
     }
-    if (sub > 0) __syncthreads();      // the previous half's join has been read
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+    if (PN_WC3_EXP & 2) {      // no join: the accumulators only have to stay alive
+      if (acc[c][0][0] + acc[c][1][3] + acc[c][2][7] == 1234.5f) J[lane] = f32x4{acc[c][0][1], acc[c][1][1], acc[c][2][1], 0.f};
+    }
+    if (sub > 0 || c > 0) __syncthreads();      // the previous half's / column set's join has been read
     // this half's share of the four output rows (A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1])
     if (sh == 0 && !(PN_WC3_EXP & 2)) {
 #pragma unroll
@@ -616,9 +709,9 @@ __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int r = 4 * g + k;
-          r0[k] = (acc[0][r] + acc[1][r]) + acc[2][r];
-          r1[k] = acc[1][r] - acc[2][r];
-          r2[k] = acc[1][r] + acc[2][r];
+          r0[k] = (acc[c][0][r] + acc[c][1][r]) + acc[c][2][r];
+          r1[k] = acc[c][1][r] - acc[c][2][r];
+          r2[k] = acc[c][1][r] + acc[c][2][r];
         }
         J[((p * 4 + 0) * 4 + g) * 64 + lane] = r0;
         J[((p * 4 + 1) * 4 + g) * 64 + lane] = r1;
@@ -634,11 +727,11 @@ __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int r = 4 * g + k;
-          const float s34 = acc[0][r] + acc[1][r], d34 = acc[0][r] - acc[1][r];
+          const float s34 = acc[c][0][r] + acc[c][1][r], d34 = acc[c][0][r] - acc[c][1][r];
           r0[k] = s34;
           r1[k] = 2.f * d34;
           r2[k] = 4.f * s34;
-          r3[k] = 8.f * d34 + acc[2][r];
+          r3[k] = 8.f * d34 + acc[c][2][r];
         }
         J[((p * 4 + 0) * 4 + g) * 64 + lane] += r0;
         J[((p * 4 + 1) * 4 + g) * 64 + lane] += r1;
@@ -649,7 +742,7 @@ __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
     __syncthreads();
     for (int vw = w; vw < ((PN_WC3_EXP & 4) ? 0 : 16); vw += NW) {
       const int g = vw >> 2, row = vw & 3;
-      const int c0 = ctile * 32 + 8 * g + 4 * lh;
+      const int c0 = (ctile * NC + c) * 32 + 8 * g + 4 * lh;
       if constexpr (QT == 1) {
         wchain_finish<1>(
             a, c0, li, lh, lo, [&](int q, int) { return J[((q * 4 + row) * 4 + g) * 64 + lane]; },
@@ -677,7 +770,7 @@ __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
           for (int px = 0; px < 4; ++px) *reinterpret_cast<f32x4*>(o + (size_t)px * a.out_ps) = y[px];
         }
         if (a.vout) {
-          f32x4* cr = carry + ((row * 4 + g) * 2 + lh) * 5;
+          f32x4* cr = carry + (((c * 4 + row) * 4 + g) * 2 + lh) * 5;
           f32x4 l, rr;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -727,6 +820,7 @@ __global__ __launch_bounds__(64 * 12) void conv_wchain3_kernel(WChainArgs a) {
           }
         }
       }
+    }
     }
   }
 }
@@ -1051,6 +1145,26 @@ static void launch_chain2_multi(const WChainMulti& m, hipStream_t st, bool prof,
   else hipLaunchKernelGGL((conv_wchain2_multi_kernel<KS, CT, QT>), grid, dim3(64 * NW), smem, st, m);
 }
 
+// F(4,3) x F(4,3): 32-column sets per block (conv_wchain3_kernel's NC).  Two (64 output channels: the input rows and their height transform
+// serve twice the MFMAs) where cout allows it and the grid keeps at least 128 blocks -- half a round of the chip, the regime the form is taken
+// in (other frames in flight take the rest); one otherwise.  PN_WCHAIN3_COLS = 1 / 2 forces a width (measurement; 2 still needs cout % 64 == 0).
+static int wino44_cols(int cout, int qtiles) {
+  static const int force = [] { const char* e = getenv("PN_WCHAIN3_COLS"); return e ? atoi(e) : 0; }();
+  if (cout % 64) return 1;
+  if (force == 1 || force == 2) return force;
+  return (long long)qtiles * (cout / 64) >= 128 ? 2 : 1;
+}
+
+template <int QT, int NC>
+static void launch_chain3(const WChainArgs& a, dim3 grid, hipStream_t st, bool prof, const pn::ProfileSlot& ps) {
+  constexpr size_t smem = (size_t)6 * 4 * 4 * 64 * 16 + (size_t)NC * 4 * 4 * 2 * 5 * 16;      // the join + the carries of the two-half form
+  static bool done[64] = {false};
+  if (pn::first_use_on_device(done))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wchain3_kernel<QT, NC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (prof) hipExtLaunchKernelGGL((conv_wchain3_kernel<QT, NC>), grid, dim3(64 * 12), smem, st, ps.start, ps.stop, 0, a);
+  else hipLaunchKernelGGL((conv_wchain3_kernel<QT, NC>), grid, dim3(64 * 12), smem, st, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1279,7 +1393,8 @@ int pn_conv2d_wino44_chain_f32(const pn_conv_desc* d, const float* planes_in, co
   a.total_quads = d->batch * a.H * a.Wq;
   const int qt2 = a.Wq == 64 ? 2 : 1;
   a.qtiles = (a.total_quads / 4) / (32 * qt2);
-  a.ctiles = d->cout / 32;
+  const int nc = wino44_cols(d->cout, a.qtiles);
+  a.ctiles = d->cout / (32 * nc);
   a.cg_in = d->cin / 8; a.cg_out = d->cout / 8;
   a.cout_pad = pn::cdiv(d->cout, 128) * 128;
   a.plane_bytes = (unsigned)((size_t)d->batch * (a.H + 2) * a.Wq * 16);
@@ -1288,21 +1403,16 @@ int pn_conv2d_wino44_chain_f32(const pn_conv_desc* d, const float* planes_in, co
 #ifdef PN_WCHAIN_STAMP
   a.stamps = pn_wchain_stamp_buffer;
 #endif
-  constexpr size_t smem = (size_t)6 * 4 * 4 * 64 * 16 + (size_t)4 * 4 * 2 * 5 * 16;      // the join + the carry of the two-half form
-  static bool done[64] = {false};
-  if (pn::first_use_on_device(done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wchain3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wchain3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
   pn::ProfileSlot ps{};
   const bool prof = pn::take_profile_slot(ps);
   const dim3 grid((unsigned)(a.qtiles * a.ctiles));
+  hipStream_t st = pn::S(stream);
   if (qt2 == 2) {
-    if (prof) hipExtLaunchKernelGGL(conv_wchain3_kernel<2>, grid, dim3(64 * 12), smem, pn::S(stream), ps.start, ps.stop, 0, a);
-    else hipLaunchKernelGGL(conv_wchain3_kernel<2>, grid, dim3(64 * 12), smem, pn::S(stream), a);
+    if (nc == 2) launch_chain3<2, 2>(a, grid, st, prof, ps);
+    else launch_chain3<2, 1>(a, grid, st, prof, ps);
   } else {
-    if (prof) hipExtLaunchKernelGGL(conv_wchain3_kernel<1>, grid, dim3(64 * 12), smem, pn::S(stream), ps.start, ps.stop, 0, a);
-    else hipLaunchKernelGGL(conv_wchain3_kernel<1>, grid, dim3(64 * 12), smem, pn::S(stream), a);
+    if (nc == 2) launch_chain3<1, 2>(a, grid, st, prof, ps);
+    else launch_chain3<1, 1>(a, grid, st, prof, ps);
   }
   return pn::check_launch("conv_wchain3_kernel");
 }
