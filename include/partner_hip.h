@@ -1321,9 +1321,12 @@ int pn_crop_roll_f32(const float *y, int batch, int h, int w, int hp, int wp, in
 int pn_scale_channels_f32(const float *x, const float *scale, size_t n, int c, float *y, pn_stream_t stream);
 int pn_recip_clamp_f32(const float *x, float lo, int n, float *y, pn_stream_t stream);
 int pn_recip_clamp_bwd_f32(const float *x, const float *dy, float lo, int n, float *dx, pn_stream_t stream);
-/* F.normalize over rows of c values (cosine attention, swin_transformer_v2.py:156-158) and its backward; inv_norm[rows] */
+/* F.normalize over rows of c values (cosine attention, swin_transformer_v2.py:156-158) and its backward; inv_norm[rows] =
+ * 1 / max(||x||, eps).  The backward takes the forward's y, inv_norm and eps: dx = inv_norm * (dy - y (y . dy)) for rows with
+ * ||x|| > eps, and dx = dy / eps for the rows the forward clamped (||x|| <= eps, all-zero rows included), which is torch
+ * autograd's gradient of F.normalize (the clamp passes nothing to the norm; at ||x|| == eps exactly torch takes the other branch). */
 int pn_l2_normalize_f32(const float *x, long long rows, int c, float eps, float *y, float *inv_norm, pn_stream_t stream);
-int pn_l2_normalize_bwd_f32(const float *y, const float *dy, const float *inv_norm, long long rows, int c, float *dx,
+int pn_l2_normalize_bwd_f32(const float *y, const float *dy, const float *inv_norm, long long rows, int c, float eps, float *dx,
                             pn_stream_t stream);
 
 /* next-4  ego-motion warp of the previous sweep's feature maps for the bidirectional context padding

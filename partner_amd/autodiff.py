@@ -360,7 +360,7 @@ def l2_normalize(t: Tape, x: Node, eps=1e-12) -> Node:
 
     def bw(dy):
         dx = torch.empty_like(dy)
-        hip.call("pn_l2_normalize_bwd_f32", y.data_ptr(), dy.data_ptr(), inv.data_ptr(), rows, c, dx.data_ptr(), hip.stream())
+        hip.call("pn_l2_normalize_bwd_f32", y.data_ptr(), dy.data_ptr(), inv.data_ptr(), rows, c, float(eps), dx.data_ptr(), hip.stream())
         accumulate(x, dx, own=True)
 
     return t.new(y, bw)

@@ -328,8 +328,11 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ x
   for (int k = lane; k < c; k += 64) y[row * c + k] = x[row * c + k] * inv;
   if (lane == 0 && inv_norm) inv_norm[row] = inv;
 }
+// rows whose norm the forward clamped (||x|| <= eps, the all-zero rows among them) have the constant divisor eps: dx = dy / eps, as
+// torch's clamp_min passes no gradient to the norm there.  The forward stored inv_norm = 1 / fmaxf(norm, eps), so a row was clamped
+// exactly when its inv_norm equals 1 / eps computed the same way.
 __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, const float* __restrict__ inv_norm,
-                                                         long long rows, int c, float* __restrict__ dx) {
+                                                         long long rows, int c, float eps, float* __restrict__ dx) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -337,7 +340,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
   for (int k = lane; k < c; k += 64) d += y[row * c + k] * dy[row * c + k];
   d = pn::wave_sum(d);
   const float inv = inv_norm[row];
-  for (int k = lane; k < c; k += 64) dx[row * c + k] = inv * (dy[row * c + k] - y[row * c + k] * d);   // norm above eps (clamped rows: dx = dy / eps, not handled)
+  if (inv == 1.f / eps) d = 0.f;
+  for (int k = lane; k < c; k += 64) dx[row * c + k] = inv * (dy[row * c + k] - y[row * c + k] * d);
 }
 
 
@@ -508,9 +512,10 @@ int pn_l2_normalize_f32(const float* x, long long rows, int c, float eps, float*
   return pn::check_launch("l2norm_kernel");
 }
 
-int pn_l2_normalize_bwd_f32(const float* y, const float* dy, const float* inv_norm, long long rows, int c, float* dx, pn_stream_t stream) {
+int pn_l2_normalize_bwd_f32(const float* y, const float* dy, const float* inv_norm, long long rows, int c, float eps, float* dx,
+                            pn_stream_t stream) {
   PN_REQUIRE(y && dy && inv_norm && dx && rows >= 1 && c >= 1, "l2_normalize_bwd: bad arguments");
-  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, pn::S(stream), y, dy, inv_norm, rows, c, dx);
+  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, pn::S(stream), y, dy, inv_norm, rows, c, eps, dx);
   return pn::check_launch("l2norm_bwd_kernel");
 }
 

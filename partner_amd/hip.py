@@ -283,7 +283,7 @@ SIGNATURES = {
     "pn_scatter_rows_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "pn_roll_w_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "pn_l2_normalize_f32": (_I, [_P, C.c_longlong, _I, _F, _P, _P, _P]),
-    "pn_l2_normalize_bwd_f32": (_I, [_P, _P, _P, C.c_longlong, _I, _P, _P]),
+    "pn_l2_normalize_bwd_f32": (_I, [_P, _P, _P, C.c_longlong, _I, _F, _P, _P]),
     "pn_nchw_to_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "pn_nhwc_to_nchw_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "pn_grad_norm_workspace_bytes": (_SZ, []),
