@@ -72,6 +72,51 @@ def _workspace(nbytes: int, dev) -> torch.Tensor:
     return t
 
 
+class PackedLayouts:
+    """The packed copies of ONE weight (ConvLayer, ConvDgrad) and which of them are up to date.  ``add(name, pack)`` registers a layout
+    when its buffer is allocated; ``pack(weight, stream)`` fills that buffer and holds the buffer, not the layer (no reference cycle:
+    the tapes build layers per iteration and their buffers must go when the layer goes).  A layout is stale until it is first packed.
+    LAZY: ``refresh`` packs nothing; a layout is packed by the next call that takes it (``ensure``) or by ``prepack_used``."""
+
+    def __init__(self, weight):
+        self.weight, self.token = weight, None      # the latest weight (a reference, no copy); the token of the last refresh
+        self.packs, self.stale, self.used = {}, set(), set()
+
+    def add(self, name: str, pack, now: bool = False) -> None:
+        self.packs[name] = pack
+        self.stale.add(name)
+        if now:
+            self.pack(name)
+
+    def refresh(self, weight, token=None) -> bool:
+        """a new weight: every layout is stale.  False, and nothing changes, when ``token`` is the token of the previous call"""
+        if token is not None and token is self.token:
+            return False
+        self.weight, self.token = weight, token
+        self.stale.update(self.packs)
+        return True
+
+    def pack(self, name: str) -> None:
+        """pack the layout from the latest weight, on the current stream, if it is stale"""
+        if name in self.stale:
+            self.stale.discard(name)
+            self.packs[name](self.weight, hip.stream())
+
+    def ensure(self, name: str) -> None:
+        """``pack`` for a call that takes the layout: it counts as used from now on"""
+        self.used.add(name)
+        self.pack(name)
+
+    def prepack_used(self) -> None:
+        for name in sorted(self.used):
+            self.ensure(name)
+
+
+def pack_call(entry: str, buf: torch.Tensor, *dims):
+    """the ``pack`` of a layout whose kernel is ``entry(weight, *dims, buffer, stream)``"""
+    return lambda w, st: hip.call(entry, w.data_ptr(), *dims, buf.data_ptr(), st)
+
+
 def to_bf16(x: torch.Tensor) -> torch.Tensor:
     """f32 -> bf16 (round to nearest even) on the HIP kernel; same shape"""
     hip.require_device(x)

@@ -99,6 +99,23 @@ def disable_conv_profiling() -> None:
     S.profiler = None
 
 
+def _tap_pack(buf: torch.Tensor, tap_n: int, cout: int, cin: int):
+    """PackedLayouts pack of the (9 cout, cin) tap matrix, row t * cout + co"""
+    def pack(w, st):
+        w9 = torch.zeros((tap_n, cin), dtype=torch.float32, device=w.device)
+        w9[:9 * cout] = w.reshape(cout, -1, 9)[:, :cin].permute(2, 0, 1).reshape(9 * cout, -1)
+        hip.call("pn_pack_linear_weight_f32", w9.data_ptr(), tap_n, cin, buf.data_ptr(), st)
+    return pack
+
+
+def _transposed_pack(layout: str, buf: torch.Tensor, cout: int, cin: int, keep: dict):
+    """PackedLayouts pack of a chained layout for the kernel with kh and kw swapped"""
+    def pack(w, st):
+        keep[layout] = wt = w.detach().float().transpose(2, 3).contiguous()   # (the launch is asynchronous: the transposed copy stays referenced, one per layout)
+        hip.call(f"pn_pack_conv_weight_{layout}_f32", wt.data_ptr(), cout, cin, buf.data_ptr(), st)
+    return pack
+
+
 # F(4, 3) (conv_wino4.hip): PN_CONV_WINO4=0 keeps F(2, 3); taken from this many 32-quad x 32-column tiles on (the kernel's K-split form
 # runs one block per such tile, the plain form one per 32 quads x 128 columns when those fill the chip).  Measured against F(2, 3):
 # 256 x 256 x 128 -> 128: 79 us / 112; 128 x 128 x 128 -> 128 (512 tiles): 27 / 31; 64 x 64 x 256 -> 256 (256 tiles): 31 / 37;
@@ -123,6 +140,10 @@ class ConvLayer:
         self.pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
         assert dtype in ("f32", "bf16")
         self.dtype = dtype
+        self.packed_rows = self.wino44_packed = None
+        self.wino4_max_pixels = None     # F(4, 3) on maps of up to this many pixels only (the training steps set it)
+        self._chain_t, self._chain_t_src = {}, {}      # the packs for the TRANSPOSED kernel a chain on a transposed map takes, and their weights (lazy)
+        self._packs = PackedLayouts(w)
         if dtype == "bf16":
             # bf16 activations / weights, f32 accumulate (pn_conv2d_nhwc_bf16)
             if deconv2x2:
@@ -141,7 +162,7 @@ class ConvLayer:
                 self._bf16_general = (w, cout_t, cin_g, kh, kw, pack_groups)      # (a reference to the caller's f32 weight, no copy)
                 if pack_groups == 1:
                     self._pack_bf16_rows(lib, w, cout_t, cin_g, kh, kw, st)
-                if getattr(self, "packed_rows", None) is None:
+                if self.packed_rows is None:
                     self._ensure_bf16_general()      # no rows form for this shape: the general layout is the one that runs
                 # (with a rows form the general layout is packed only if a call ever needs it -- one packed copy per layer, not two)
         elif deconv2x2:
@@ -149,13 +170,13 @@ class ConvLayer:
             assert tuple(w.shape[2:]) == (2, 2)
             self.cin, self.cout, self.kh, self.kw = cin, cout, 1, 1
             self.packed = _f32(lib.pn_deconv2x2_packed_weight_floats(cin, cout), dev)
-            hip.call("pn_pack_deconv2x2_weight_f32", w.data_ptr(), cin, cout, self.packed.data_ptr(), st)
+            self._packs.add("direct", pack_call("pn_pack_deconv2x2_weight_f32", self.packed, cin, cout), now=True)
         else:
             pack_groups = self.range_strata if self.range_strata > 1 else self.groups
             cout_t, cin_g, kh, kw = w.shape
             self.cin, self.cout, self.kh, self.kw = cin_g, cout_t // pack_groups, kh, kw
             self.packed = _f32(lib.pn_conv_packed_weight_floats(self.cout, cin_g, kh, kw, pack_groups), dev)
-            hip.call("pn_pack_conv_weight_f32", w.data_ptr(), cout_t, cin_g, kh, kw, pack_groups, self.packed.data_ptr(), st)
+            self._packs.add("direct", pack_call("pn_pack_conv_weight_f32", self.packed, cout_t, cin_g, kh, kw, pack_groups), now=True)
         self.scale = None if scale is None else scale.detach().contiguous().float()
         self.shift = None if shift is None else shift.detach().contiguous().float()
         self.out_channels = self.cout * (self.groups if not deconv2x2 else 1)
@@ -166,20 +187,17 @@ class ConvLayer:
         if (dtype == "f32" and not deconv2x2 and self.range_strata <= 1 and self.groups == 1 and (self.kh, self.kw) == (3, 3)
                 and self.stride == 1 and self.pad == (1, 1) and self.cin % 4 == 0 and R.conv_wino):
             self.wino_packed = _f32(lib.pn_conv_wino_packed_weight_floats(self.cout, self.cin), dev)
-            hip.call("pn_pack_conv_weight_wino_f32", w.data_ptr(), self.cout, self.cin, self.wino_packed.data_ptr(), st)
+            self._packs.add("wino", pack_call("pn_pack_conv_weight_wino_f32", self.wino_packed, self.cout, self.cin), now=True)
         # ... and the F(4, 3) weights (4.5 MFMA equivalents per output) when the kernel's 32-column wave tiles fit the layer
         self.wino4_packed = None
         if self.wino_packed is not None and R.conv_wino4 and wino4 and self.cout % 32 == 0 and self.act in (ACT_NONE, ACT_RELU):
             self.wino4_packed = _f32(lib.pn_conv_wino4_packed_weight_floats(self.cout, self.cin), dev)
-            hip.call("pn_pack_conv_weight_wino4_f32", w.data_ptr(), self.cout, self.cin, self.wino4_packed.data_ptr(), st)
+            self._packs.add("wino4", pack_call("pn_pack_conv_weight_wino4_f32", self.wino4_packed, self.cout, self.cin), now=True)
         # ... and the F(2, 3) x F(4, 3) weights of the chained form (conv_wchain.hip, ops.conv_chain: 3 MFMA equivalents per output)
         self.wino24_packed = None
-        self._w_ref = None               # the layer's weight, for the packs of the TRANSPOSED kernel a chain on a transposed map takes (lazy)
-        self._chain_t: dict = {}
         if self.wino4_packed is not None and R.conv_chain2d and self.cin % 32 == 0:
             self.wino24_packed = _f32(lib.pn_conv_wino24_packed_weight_floats(self.cout, self.cin), dev)
-            hip.call("pn_pack_conv_weight_wino24_f32", w.data_ptr(), self.cout, self.cin, self.wino24_packed.data_ptr(), st)
-            self._w_ref = w
+            self._packs.add("wino24", pack_call("pn_pack_conv_weight_wino24_f32", self.wino24_packed, self.cout, self.cin), now=True)
 
         # ... and 3x3 layers with one to three output channels over many input channels (the geometry-aware head's 256 -> 1 heat-map and
         # vote-class convolutions): a GEMM over the pixels against the (9 cout, cin) tap matrix + a nine-term shifted sum
@@ -189,7 +207,9 @@ class ConvLayer:
                 and self.pad == (1, 1) and self.cout <= 3 and self.cin >= 128 and self.cin % 4 == 0 and R.conv_tapsum and R.linear):
             self.tap_n = (9 * self.cout + 3) // 4 * 4
             self.tap_packed = _f32(lib.pn_linear_packed_weight_floats(self.tap_n, self.cin), dev)
-            self._pack_taps(w)
+            self._packs.add("tap", _tap_pack(self.tap_packed, self.tap_n, self.cout, self.cin), now=True)
+        if self.wino24_packed is None:      # no chained 2-D form: chain_weights adds no layout later (it asserts so, and _chain_orientation
+            self._packs.weight = None       # refuses the transposed map): the constructor's weight is not kept
 
     def _ensure_bf16_general(self) -> None:
         if self.packed is None:
@@ -201,7 +221,6 @@ class ConvLayer:
     def _pack_bf16_rows(self, lib, w: torch.Tensor, rows: int, cin: int, kh: int, kw: int, st) -> None:
         """the [row][tap][cin] weights of the bf16 implicit-GEMM kernel (csrc/conv_bf16.hip, r5): the layers of the Waymo BEV maps -- cin a
         multiple of 64, cout of 16 -- run there, every other bf16 layer on the general kernel (pn_conv2d_nhwc_bf16)"""
-        self.packed_rows = None
         if cin % 64 == 0 and self.cout % 16 == 0 and self.act in (ACT_NONE, ACT_RELU):
             self.packed_rows = torch.empty(lib.pn_conv_bf16_rows_packed_elems(rows, cin, kh, kw), dtype=torch.bfloat16, device=w.device)
             hip.call("pn_pack_conv_weight_bf16_rows", w.data_ptr(), rows, cin, kh, kw, self.packed_rows.data_ptr(), st)
@@ -221,7 +240,7 @@ class ConvLayer:
         b, h, w, ct = x.shape
         d = self.planes_desc(b, h, w, ct, in_channel_offset)
         assert d is not None, "ConvLayer.to_planes: check planes_desc first"
-        self._ensure("direct")
+        self._packs.ensure("direct")
         oh, ow = self.out_hw(h, w)
         assert planes.numel() >= hip.load().pn_wino4_planes_floats(b, oh, ow, self.cout)
         st = hip.stream()
@@ -233,44 +252,25 @@ class ConvLayer:
         if prof is not None:
             prof.end(ev, 2.0 * b * oh * ow * self.cout * self.cin * self.kh * self.kw, st, tag=f"{oh}x{ow} {self.cin}->{self.cout} k{self.kh} -> planes")
 
-    def chain_weights(self, two_d: bool, transposed: bool) -> torch.Tensor:
-        """packed weights of the chained F(4,3) / F(2,3)xF(4,3) forms; ``transposed``: of the kernel with kh and kw swapped (the chain then runs
-        on the transposed map), packed on first use.  The transposed layouts belong to the inference path (the head's
-        branch chain): they are not tracked by ``prepack_used`` and a stale one is repacked lazily on the caller's stream"""
-        key = "wino44" if two_d == "wino44" else ("wino24" if two_d else "wino4")
-        if not transposed:
-            if key == "wino44" and getattr(self, "wino44_packed", None) is None:      # F(4,3) x F(4,3) (r5): packed on first use
-                lib, w = hip.load(), getattr(self, "_stale_w", None)
-                w = self._w_ref if w is None else w
-                self.wino44_packed = _f32(lib.pn_conv_wino44_packed_weight_floats(self.cout, self._pack_cin), w.device)
-                hip.call("pn_pack_conv_weight_wino44_f32", w.data_ptr(), self.cout, self._pack_cin, self.wino44_packed.data_ptr(), hip.stream())
-                self.__dict__.setdefault("_used", set()).add("wino44")
-                (getattr(self, "_stale", None) or set()).discard("wino44")
-                return self.wino44_packed
-            self._ensure(key)
-            return {"wino44": getattr(self, "wino44_packed", None), "wino24": self.wino24_packed, "wino4": self.wino4_packed}[key]
-        stale = getattr(self, "_stale", None) or ()
-        if key not in self._chain_t or (key + "_t") in stale:
-            lib, w = hip.load(), getattr(self, "_stale_w", None)
-            w = self._w_ref if w is None else w
-            wt = w.detach().float().transpose(2, 3).contiguous()
-            fam = key
-            buf = self._chain_t.get(key)
-            if buf is None:
-                buf = _f32(getattr(lib, f"pn_conv_{fam}_packed_weight_floats")(self.cout, self._pack_cin), w.device)
-            hip.call(f"pn_pack_conv_weight_{fam}_f32", wt.data_ptr(), self.cout, self._pack_cin, buf.data_ptr(), hip.stream())
-            self._chain_t[key] = buf
-            if not isinstance(getattr(self, "_chain_t_src", None), dict):
-                self._chain_t_src = {}
-            self._chain_t_src[key] = wt   # (the launch is asynchronous: the transposed copy stays referenced, one per layout)
-            if stale:
-                stale.discard(key + "_t")
-        return self._chain_t[key]
-
-    def _pack_taps(self, w: torch.Tensor) -> None:
-        w9 = torch.zeros((self.tap_n, self.cin), dtype=torch.float32, device=w.device)
-        w9[:9 * self.cout] = w.reshape(self.cout, -1, 9)[:, :self.cin].permute(2, 0, 1).reshape(9 * self.cout, -1)   # row t * cout + co
-        hip.call("pn_pack_linear_weight_f32", w9.data_ptr(), self.tap_n, self.cin, self.tap_packed.data_ptr(), hip.stream())
+    def chain_weights(self, layout: str, transposed: bool) -> torch.Tensor:
+        """packed weights of a chained form (``layout``: "wino4" F(4,3), "wino24" F(2,3)xF(4,3), "wino44" F(4,3)xF(4,3)); ``transposed``: of the
+        kernel with kh and kw swapped (the chain then runs on the transposed map).  F(4,3)xF(4,3) (r5) and the transposed layouts are
+        allocated and packed on first use.  The transposed layouts belong to the inference path (the head's branch chain): they are
+        not tracked by ``prepack_used`` and a stale one is repacked lazily on the caller's stream"""
+        cout, cin = self.cout, self._pack_cin
+        if transposed:
+            if layout not in self._chain_t:
+                assert self._packs.weight is not None, "chain_weights: only layers with wino24_packed keep the weight the transposed layouts are packed from"
+                buf = self._chain_t[layout] = _f32(getattr(hip.load(), f"pn_conv_{layout}_packed_weight_floats")(cout, cin), self.packed.device)
+                self._packs.add(layout + "_t", _transposed_pack(layout, buf, cout, cin, self._chain_t_src))
+            self._packs.pack(layout + "_t")
+            return self._chain_t[layout]
+        if layout == "wino44" and self.wino44_packed is None:
+            assert self._packs.weight is not None, "chain_weights: only layers with wino24_packed keep the weight F(4,3)xF(4,3) is packed from"
+            self.wino44_packed = _f32(hip.load().pn_conv_wino44_packed_weight_floats(cout, cin), self.packed.device)
+            self._packs.add("wino44", pack_call("pn_pack_conv_weight_wino44_f32", self.wino44_packed, cout, cin))
+        self._packs.ensure(layout)
+        return {"wino44": self.wino44_packed, "wino24": self.wino24_packed, "wino4": self.wino4_packed}[layout]
 
     def repack(self, weight: torch.Tensor, shift: Optional[torch.Tensor] = None, token=None) -> None:
         """refresh the packed copies from an updated weight of the same shape (training: once per step).  LAZY: a layout (direct,
@@ -279,54 +279,15 @@ class ConvLayer:
         training steps hand in views of their flat parameter buffer, which the optimizer rewrites only after the backward.
         ``token``: a call with the token of the previous call is a no-op (the training steps refresh every layer once at the start of an
         iteration, ``prepack_used``, and pass the iteration's token from the layers' forward / backward)"""
-        if token is not None and getattr(self, "_token", None) is token:
+        if not self._packs.refresh(weight.detach(), token):
             return
-        self._token = token
-        w = weight.detach()
-        assert w.is_contiguous() and w.dtype == torch.float32
-        self._stale_w = w
-        self._stale = {"direct"} | ({"wino"} if self.wino_packed is not None else set()) | ({"wino4"} if self.wino4_packed is not None else set())
-        if self.tap_packed is not None:
-            self._stale.add("tap")
-        if getattr(self, "wino24_packed", None) is not None:
-            self._stale.add("wino24")
-        if getattr(self, "wino44_packed", None) is not None:
-            self._stale.add("wino44")
-        for k in getattr(self, "_chain_t", {}):
-            self._stale.add(k + "_t")
+        assert self._packs.weight.is_contiguous() and self._packs.weight.dtype == torch.float32
         if shift is not None:
             self.shift = shift
 
     def prepack_used(self) -> None:
         """pack, on the current stream, the layouts the layer's calls have taken so far (after ``repack``)"""
-        for layout in sorted(getattr(self, "_used", ())):
-            self._ensure(layout)
-
-    def _ensure(self, layout: str) -> None:
-        if not layout.endswith("_t"):
-            self.__dict__.setdefault("_used", set()).add(layout)
-        stale = getattr(self, "_stale", None)
-        if not stale or layout not in stale:
-            return
-        stale.discard(layout)
-        w, st = self._stale_w, hip.stream()
-        if layout == "direct":
-            if self.deconv2x2:
-                hip.call("pn_pack_deconv2x2_weight_f32", w.data_ptr(), self._pack_cin, self.cout, self.packed.data_ptr(), st)
-            else:
-                pack_groups = self.range_strata if self.range_strata > 1 else self.groups
-                hip.call("pn_pack_conv_weight_f32", w.data_ptr(), w.shape[0], self._pack_cin, self.kh, self.kw, pack_groups,
-                         self.packed.data_ptr(), st)
-        elif layout == "tap":
-            self._pack_taps(w)
-        elif layout == "wino":
-            hip.call("pn_pack_conv_weight_wino_f32", w.data_ptr(), self.cout, self._pack_cin, self.wino_packed.data_ptr(), st)
-        elif layout == "wino24":
-            hip.call("pn_pack_conv_weight_wino24_f32", w.data_ptr(), self.cout, self._pack_cin, self.wino24_packed.data_ptr(), st)
-        elif layout == "wino44":
-            hip.call("pn_pack_conv_weight_wino44_f32", w.data_ptr(), self.cout, self._pack_cin, self.wino44_packed.data_ptr(), st)
-        else:
-            hip.call("pn_pack_conv_weight_wino4_f32", w.data_ptr(), self.cout, self._pack_cin, self.wino4_packed.data_ptr(), st)
+        self._packs.prepack_used()
 
     def _use_wino(self, b: int, h: int, w: int, accumulate: bool) -> bool:
         if self.wino_packed is None or accumulate or w % 2 or self.cin != self._pack_cin:
@@ -335,7 +296,8 @@ class ConvLayer:
         return tiles >= R.conv_wino_min_tiles
 
     def _use_wino4(self, b: int, h: int, w: int, accumulate: bool) -> bool:   # (the tile-count gate below is about leaving the direct kernel, not about the form)
-        if self.wino4_packed is None or accumulate or w % 4 or self.cin != self._pack_cin or h * w > getattr(self, "wino4_max_pixels", 1 << 62):
+        if (self.wino4_packed is None or accumulate or w % 4 or self.cin != self._pack_cin
+                or (self.wino4_max_pixels is not None and h * w > self.wino4_max_pixels)):
             return False
         return ((b * h * (w // 4) + 31) // 32) * (self.cout // 32) >= R.conv_wino4_min_tiles
 
@@ -373,7 +335,7 @@ class ConvLayer:
             prof = S.profiler
             if prof is not None:
                 ev = prof.begin(st)
-            igemm = getattr(self, "packed_rows", None) is not None and hip.load().pn_conv2d_igemm_bf16_supported(C.byref(d)) == 1
+            igemm = self.packed_rows is not None and hip.load().pn_conv2d_igemm_bf16_supported(C.byref(d)) == 1
             if igemm:
                 hip.call("pn_conv2d_igemm_bf16", C.byref(d), x.data_ptr(), self.packed_rows.data_ptr(), hip.ptr(self.scale), hip.ptr(self.shift),
                          out.data_ptr(), int(out.dtype == torch.float32), st)
@@ -400,7 +362,7 @@ class ConvLayer:
         use_wino4 = not use_tap and self._use_wino4(b, h, w, accumulate)
         use_wino = not use_tap and not use_wino4 and self._use_wino(b, h, w, accumulate)
         assert use_wino4 or not out_transposed, "ConvLayer: a transposed output needs the F(4,3) kernel (check _use_wino4 first)"
-        self._ensure("tap" if use_tap else "wino4" if use_wino4 else "wino" if use_wino else "direct")
+        self._packs.ensure("tap" if use_tap else "wino4" if use_wino4 else "wino" if use_wino else "direct")
         if use_tap:
             m = b * h * w
             g = torch.empty((m, self.tap_n), dtype=torch.float32, device=x.device)
@@ -452,7 +414,7 @@ def _chain_orientation(layers, b: int, h: int, w: int):
         if l.dtype != "f32" or l.wino4_packed is None or l.cin != l._pack_cin or (k and l.cin != layers[k - 1].cout):
             return None
     for transposed in (False, True):
-        if transposed and any(getattr(l, "_w_ref", None) is None for l in layers):
+        if transposed and any(l.wino24_packed is None for l in layers):      # (the transposed packs are kept for layers with the 2-D chained form only)
             break
         if all(lib.pn_conv_wino4_chain_supported(C.byref(_chain_desc(l, b, h, w, transposed=transposed))) for l in layers):
             return transposed
@@ -528,22 +490,30 @@ def conv_chain(layers, x: Optional[torch.Tensor], out: Optional[torch.Tensor] = 
     for k, l in enumerate(layers):
         is_last = k == len(layers) - 1
         d = _chain_desc(l, b, h, w, out.shape[3], out_channel_offset, transposed=tr) if is_last else _chain_desc(l, b, h, w, transposed=tr)
-        two_d = l.wino24_packed is not None and _chain_two_d(lib, d)
-        if two_d and _chain_44(lib, d):
-            two_d = "wino44"
-            S.chain44_launches += 1
-        wts = l.chain_weights(two_d, tr)
+        form = "wino4"
+        if l.wino24_packed is not None and _chain_two_d(lib, d):
+            form = "wino24"
+            if _chain_44(lib, d):
+                form = "wino44"
+                S.chain44_launches += 1
+        entry, tag, divisor = _CHAIN_FORMS[form]
+        wts = l.chain_weights(form, tr)
         if prof is not None:
             ev = prof.begin(st)
         src, dst = src_dst(k)
-        hip.call("pn_conv2d_wino44_chain_f32" if two_d == "wino44" else ("pn_conv2d_wino24_chain_f32" if two_d else "pn_conv2d_wino4_chain_f32"), C.byref(d), src.data_ptr(),
-                 wts.data_ptr(), hip.ptr(l.scale), hip.ptr(l.shift),
+        hip.call(entry, C.byref(d), src.data_ptr(), wts.data_ptr(), hip.ptr(l.scale), hip.ptr(l.shift),
                  None if is_last else dst.data_ptr(), out.data_ptr() if is_last else None, st)
         if prof is not None:
             flops = 2.0 * b * h * w * l.cout * l.cin * 9
-            tag = "F(4,3)xF(4,3) chain" if two_d == "wino44" else ("F(2,3)xF(4,3) chain" if two_d else "F(4,3) chain")
-            prof.end(ev, flops, st, tag=f"{h}x{w} {l.cin}->{l.cout} k3 {tag}", issued=flops / 4.0 if two_d == "wino44" else (flops / 3.0 if two_d else None))
+            prof.end(ev, flops, st, tag=f"{h}x{w} {l.cin}->{l.cout} k3 {tag}", issued=None if divisor is None else flops / divisor)
     return out
+
+
+# the chained forms: ConvLayer.chain_weights layout -> (entry point, profiler tag, dense-convolution FLOPs per FLOP issued to the MFMA;
+# None: ConvProfiler.end reads it from the tag)
+_CHAIN_FORMS = {"wino4": ("pn_conv2d_wino4_chain_f32", "F(4,3) chain", None),
+                "wino24": ("pn_conv2d_wino24_chain_f32", "F(2,3)xF(4,3) chain", 3.0),
+                "wino44": ("pn_conv2d_wino44_chain_f32", "F(4,3)xF(4,3) chain", 4.0)}
 
 
 def _chain_two_d(lib, d) -> bool:
@@ -621,7 +591,7 @@ class PillarConvLayer:
         hip.call("pn_pack_pillar_conv_weight_f32", w.data_ptr(), self.cout, self.cin, self.packed.data_ptr(), hip.stream())
         self.scale = None if scale is None else scale.detach().contiguous().float()
         self.shift = None if shift is None else shift.detach().contiguous().float()
-        self.packed_rows = None
+        self.packed_rows = self.packed_t = self._token = None      # (packed_t: the data gradient's weights, from the first ``repack`` on)
         if self.stride == 2 and self.cin % 16 == 0 and self.cout <= 128:      # the row-band form (csrc/pillar_rows.hip) where the frame index leaves row_start
             self.packed_rows = _f32(lib.pn_pillar_conv_rows_packed_weight_floats(self.cout, self.cin), w.device)
             hip.call("pn_pack_pillar_conv_rows_weight_f32", w.data_ptr(), self.cout, self.cin, self.packed_rows.data_ptr(), hip.stream())
@@ -706,12 +676,12 @@ class PillarConvLayer:
 
     # ---- training: pair tables built once per iteration, shared by forward, data gradient and weight gradient
     def repack(self, weight: torch.Tensor, token=None) -> None:
-        if token is not None and getattr(self, "_token", None) is token:
+        if token is not None and self._token is token:
             return
         self._token = token
         w = weight.detach().contiguous().float()
         hip.call("pn_pack_pillar_conv_weight_f32", w.data_ptr(), self.cout, self.cin, self.packed.data_ptr(), hip.stream())
-        if getattr(self, "packed_t", None) is None:
+        if self.packed_t is None:
             self.packed_t = _f32(hip.load().pn_pillar_conv_packed_weight_floats(self.cin, self.cout), w.device)
         wt = w.permute(1, 0, 2, 3).contiguous()          # (Cin, Cout, 3, 3): the data gradient multiplies by W_tap^T, same tap
         hip.call("pn_pack_pillar_conv_weight_f32", wt.data_ptr(), self.cin, self.cout, self.packed_t.data_ptr(), hip.stream())
@@ -789,7 +759,7 @@ def _job_array(jobs: Sequence[ConvJob]):
     for k, jb in enumerate(jobs):
         c = arr[k]
         c.desc = jb.desc
-        jb.layer._ensure("direct")
+        jb.layer._packs.ensure("direct")
         c.in_, c.packed_w, c.out = jb.x.data_ptr(), jb.layer.packed.data_ptr(), jb.out.data_ptr()
         c.scale, c.shift = hip.ptr(jb.layer.scale), hip.ptr(jb.layer.shift)
         if jb.stats is not None:

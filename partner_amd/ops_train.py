@@ -83,58 +83,38 @@ class ConvDgrad:
         cout, cin, kh, kw = weight.shape
         self.cout, self.cin, self.kh, self.kw, self.stride, self.pad = cout, cin, kh, kw, int(stride), int(pad)
         dev = weight.device
+        self._packs = packs = PackedLayouts(weight.detach().contiguous().float())      # lazy from the start: nothing is packed here
         if self.stride == 1:
             self.kind = "s1"
             self.packed = _f32(lib.pn_conv_packed_weight_floats(cin, cout, kh, kw, 1), dev)
+            packs.add("direct", pack_call("pn_pack_conv_dgrad_weight_f32", self.packed, cout, cin, kh, kw))
         elif self.stride == 2 and (kh, kw, self.pad) == (3, 3, 1):
             self.kind = "s2k3"
             self.packed = _f32(lib.pn_conv_dgrad_s2_packed_weight_floats(cout, cin), dev)
+            packs.add("direct", pack_call("pn_pack_conv_dgrad_s2_weight_f32", self.packed, cout, cin))
         elif self.stride == 2 and (kh, kw, self.pad) == (2, 2, 0):
             self.kind = "s2k2"
             self.packed = _f32(lib.pn_deconv2x2_packed_weight_floats(cout, cin), dev)
+            packs.add("direct", pack_call("pn_pack_deconv2x2_weight_f32", self.packed, cout, cin))
         else:
             raise hip.PartnerHipError(f"ConvDgrad: unsupported geometry k={kh}x{kw} stride={stride} pad={pad}")
         # the data gradient of a 3x3 / stride-1 / pad-1 convolution is itself one (taps mirrored, channels swapped): it takes the
-        # width-Winograd kernel on large maps, like the forward layer (conv_wino.hip)
+        # width-Winograd kernel on large maps, like the forward layer (conv_wino.hip).  The pack kernels read the forward weight so
+        # (r2 made a flipped + transposed copy first: two more launches per layer and iteration)
         self.wino_packed = self.wino4_packed = None
         if self.kind == "s1" and (kh, kw, self.pad) == (3, 3, 1) and cout % 4 == 0 and R.conv_wino:
             self.wino_packed = _f32(lib.pn_conv_wino_packed_weight_floats(cin, cout), dev)
+            packs.add("wino", pack_call("pn_pack_conv_dgrad_weight_wino_f32", self.wino_packed, cout, cin))
             if R.conv_wino4 and R.conv_wino4_dgrad and cin % 32 == 0:
                 self.wino4_packed = _f32(lib.pn_conv_wino4_packed_weight_floats(cin, cout), dev)
-        self.repack(weight)
+                packs.add("wino4", pack_call("pn_pack_conv_dgrad_weight_wino4_f32", self.wino4_packed, cout, cin))
 
     def repack(self, weight: torch.Tensor, token=None) -> None:
         """lazy, as ConvLayer.repack: the layout a call takes is packed on first use"""
-        if token is not None and getattr(self, "_token", None) is token:
-            return
-        self._token = token
-        self._stale_w = weight.detach().contiguous().float()
-        self._stale = {"direct"} | ({"wino"} if self.wino_packed is not None else set()) | ({"wino4"} if self.wino4_packed is not None else set())
+        self._packs.refresh(weight.detach().contiguous().float(), token)
 
     def prepack_used(self) -> None:
-        for layout in sorted(getattr(self, "_used", ())):
-            self._ensure(layout)
-
-    def _ensure(self, layout: str) -> None:
-        self.__dict__.setdefault("_used", set()).add(layout)
-        if layout not in self._stale:
-            return
-        self._stale.discard(layout)
-        w, st = self._stale_w, hip.stream()
-        if layout == "direct":
-            if self.kind == "s1":
-                hip.call("pn_pack_conv_dgrad_weight_f32", w.data_ptr(), self.cout, self.cin, self.kh, self.kw, self.packed.data_ptr(), st)
-            elif self.kind == "s2k3":
-                hip.call("pn_pack_conv_dgrad_s2_weight_f32", w.data_ptr(), self.cout, self.cin, self.packed.data_ptr(), st)
-            else:
-                hip.call("pn_pack_deconv2x2_weight_f32", w.data_ptr(), self.cout, self.cin, self.packed.data_ptr(), st)
-            return
-        # the gradient convolution's weight is the forward one with the taps mirrored and the channels swapped: the pack kernels read it so
-        # (r2 made a flipped + transposed copy first: two more launches per layer and iteration)
-        if layout == "wino":
-            hip.call("pn_pack_conv_dgrad_weight_wino_f32", w.data_ptr(), self.cout, self.cin, self.wino_packed.data_ptr(), st)
-        else:
-            hip.call("pn_pack_conv_dgrad_weight_wino4_f32", w.data_ptr(), self.cout, self.cin, self.wino4_packed.data_ptr(), st)
+        self._packs.prepack_used()
 
     def __call__(self, dout: torch.Tensor, out: Optional[torch.Tensor] = None, dout_channel_offset=0,
                  out_channel_offset=0, accumulate=False) -> torch.Tensor:
@@ -165,15 +145,15 @@ class ConvDgrad:
         d.accumulate = int(accumulate)
         if (self.wino4_packed is not None and not accumulate and ow % 4 == 0 and cin_eff == self.cout
                 and ((b * oh * (ow // 4) + 31) // 32) * (self.cin // 32) >= R.conv_wino4_min_tiles):
-            self._ensure("wino4")
+            self._packs.ensure("wino4")
             hip.call("pn_conv2d_wino4_nhwc_f32", C.byref(d), dout.data_ptr(), self.wino4_packed.data_ptr(), None, None, out.data_ptr(), hip.stream())
             return out
         if (self.wino_packed is not None and not accumulate and ow % 2 == 0 and cin_eff == self.cout
                 and ((b * oh * (ow // 2) + 31) // 32) * ((self.cin + 63) // 64) >= R.conv_wino_min_tiles):
-            self._ensure("wino")
+            self._packs.ensure("wino")
             hip.call("pn_conv2d_wino_nhwc_f32", C.byref(d), dout.data_ptr(), self.wino_packed.data_ptr(), None, None, out.data_ptr(), hip.stream())
             return out
-        self._ensure("direct")
+        self._packs.ensure("direct")
         hip.call("pn_conv2d_nhwc_f32", C.byref(d), dout.data_ptr(), self.packed.data_ptr(), None, None, out.data_ptr(), hip.stream())
         return out
 
@@ -409,10 +389,11 @@ class StratConvDgrad:
         self._idx = idx.flip(3).permute(0, 4, 2, 1, 3).reshape(-1).contiguous()
         self._shape = (strata * 3 * cin, self.cout, 3, 1)
         self._w = weight.detach().reshape(-1)[self._idx].view(self._shape)
+        self._token = None
         self.layer = ConvLayer(self._w, stride=1, pad=(1, 0), range_strata=self.strata)
 
     def repack(self, weight: torch.Tensor, token=None) -> None:
-        if token is not None and getattr(self, "_token", None) is token:
+        if token is not None and self._token is token:
             return
         self._token = token
         torch.index_select(weight.detach().reshape(-1), 0, self._idx, out=self._w.view(-1))

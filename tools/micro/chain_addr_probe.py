@@ -6,6 +6,7 @@ import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from partner_amd import ops, hip
+from partner_amd.ops_conv import _chain_desc
 dev = torch.device("cuda:0")
 lib = hip.load()
 b, h, w, c = 1, 256, 256, 128
@@ -27,8 +28,8 @@ def run(off0, off1, reps=30):
     def chain():
         for k, l in enumerate(layers):
             last = k == 2
-            d = ops._chain_desc(l, b, h, w, c, 0, transposed=False) if last else ops._chain_desc(l, b, h, w, transposed=False)
-            wts = l.chain_weights(True, False)
+            d = _chain_desc(l, b, h, w, c, 0, transposed=False) if last else _chain_desc(l, b, h, w, transposed=False)
+            wts = l.chain_weights("wino24", False)
             hip.call("pn_conv2d_wino24_chain_f32", C.byref(d), bufs[k & 1].data_ptr(), wts.data_ptr(), hip.ptr(l.scale), hip.ptr(l.shift),
                      None if last else bufs[(k + 1) & 1].data_ptr(), out.data_ptr() if last else None, st)
     for _ in range(10):
