@@ -822,6 +822,21 @@ int pn_bilinear_upsample_add_f32(const float *low, int batch, int h, int w, int 
                                  float *out, pn_stream_t stream);
 int pn_seg_point_labels(const float *seg_sample, int h, int w, int classes, const int64_t *grid_ind,
                         int n, int64_t *labels, pn_stream_t stream);
+/* Panoptic fusion of one sample (SingleConvHead.predict_panoptic, seg_head.py:99-168): pn_seg_point_labels fused with the
+ * nearest-box search, one launch writing labels[n] and instance[n] (both int64).  seg_sample: the sample's logits (h, w, classes)
+ * with pixel_stride floats between pixels (a padded NHWC buffer is read in place).  points: the sample's first row, point_stride
+ * floats per row, x / y in columns x_col / x_col + 1 (3 for polar point rows, 0 for Cartesian ones); they are rotated by the sector
+ * angle, x' = x cos_a - y sin_a, y' = x sin_a + y cos_a (cos_a / sin_a: computed by the caller in double, rounded once to f32 as the
+ * reference's rot_mat_T).  boxes: m rows of box_stride floats, x / y first; scores (m) f32, box_labels / instances (m) int64.
+ * sem2box: DEVICE int32[classes + 1], the box label of a semantic label or -1 for stuff (entry 0 unused).  A point whose label maps
+ * to a box label takes instances[j] of the nearest centre j among the boxes with that label and score > score_thr; squared f32
+ * distances, the lowest row wins a tie (torch.argmin).  Stuff points, points whose grid_ind row lies outside the map (label 0) and
+ * things without an eligible box get instance 0.  Any m (the boxes pass through LDS in chunks of 1024); n == 0 launches nothing,
+ * m == 0 writes the labels and zeros (the box arrays may then be NULL). */
+int pn_panoptic_points_f32(const float *seg_sample, int h, int w, int classes, int pixel_stride, const int64_t *grid_ind, int n,
+                           const float *points, int point_stride, int x_col, float cos_a, float sin_a, const float *boxes,
+                           int box_stride, const float *scores, const int64_t *box_labels, const int64_t *instances, int m,
+                           const int32_t *sem2box, float score_thr, int64_t *labels, int64_t *instance, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * next-1  sparse 3-D convolutions of the middle encoder SpMiddleResNetFHD

@@ -56,6 +56,73 @@ __global__ void seg_point_labels_kernel(const float* __restrict__ seg, int H, in
   labels[i] = arg + 1;
 }
 
+// Panoptic fusion of one sample (SingleConvHead.predict_panoptic, seg_head.py:99-168): the label gather of seg_point_labels_kernel
+// fused with the nearest-box search.  A point with a thing label takes the instance id of the nearest box centre among the boxes of
+// its class with score > thr; stuff points, points outside the map and things without an eligible box get 0.
+// One lane owns one point; the block stages the boxes chunk by chunk into LDS as (x, y, label or -1 when the score is not above the
+// threshold) in their original order, and every lane scans the chunk: all lanes read the same entry (one 16-byte broadcast read, no
+// bank conflict).  The winner is kept as its ROW, the int64 id is fetched once at the end.  Squared distances, strict '<': the first
+// of equal distances wins, as torch.argmin.  256 threads and 1024 boxes (16 KiB of LDS) per block: 8 blocks fit a CU's LDS, so the
+// wave slots, not the LDS, bound the occupancy; the sweep's few hundred boxes are one chunk.
+constexpr int kPanopticBlock = 256;
+constexpr int kPanopticChunk = 1024;
+
+__global__ __launch_bounds__(kPanopticBlock) void panoptic_points_kernel(
+    const float* __restrict__ seg, int H, int W, int C, int pixel_stride, const int64_t* __restrict__ grid_ind, int n,
+    const float* __restrict__ points, int point_stride, int x_col, float cos_a, float sin_a, const float* __restrict__ boxes, int box_stride,
+    const float* __restrict__ scores, const int64_t* __restrict__ box_labels, const int64_t* __restrict__ instances, int m,
+    const int32_t* __restrict__ sem2box, float score_thr, int64_t* __restrict__ labels, int64_t* __restrict__ instance) {
+  __shared__ float4 sbox[kPanopticChunk];
+  const int i = blockIdx.x * kPanopticBlock + threadIdx.x;
+  int want = -1;          // box label this point looks for; -1: stuff, outside the map, or past the end
+  float px = 0.f, py = 0.f;
+  if (i < n) {
+    const int64_t y = grid_ind[(size_t)i * 3 + 1], x = grid_ind[(size_t)i * 3 + 2];
+    int lab = 0;
+    if (y >= 0 && y < H && x >= 0 && x < W) {
+      const float* p = seg + ((size_t)y * W + x) * pixel_stride;
+      float top = p[0];
+      int arg = 0;
+      for (int c = 1; c < C; ++c)
+        if (p[c] > top) { top = p[c]; arg = c; }
+      lab = arg + 1;
+      want = sem2box[lab];
+    }
+    labels[i] = lab;
+    if (want >= 0) {
+      // the sector's points into the sweep's frame: points[:, x:x+2] @ [[cos, sin], [-sin, cos]] in f32 (seg_head.py:124-127, 159)
+      const float* q = points + (size_t)i * point_stride + x_col;
+      const float qx = q[0], qy = q[1];
+      px = qx * cos_a - qy * sin_a;
+      py = qx * sin_a + qy * cos_a;
+    }
+  }
+  float best = 0.f;
+  int best_row = -1;
+  for (int c0 = 0; c0 < m; c0 += kPanopticChunk) {
+    const int cnt = min(kPanopticChunk, m - c0);
+    if (c0) __syncthreads();      // every lane is done with the previous chunk
+    for (int j = threadIdx.x; j < cnt; j += kPanopticBlock) {
+      const size_t r = (size_t)(c0 + j);
+      const int64_t bl = box_labels[r];
+      const int lab = (scores[r] > score_thr && bl >= 0 && bl <= 0x7fffffff) ? (int)bl : -1;
+      sbox[j] = make_float4(boxes[r * box_stride], boxes[r * box_stride + 1], __int_as_float(lab), 0.f);
+    }
+    __syncthreads();
+    if (want >= 0) {
+      for (int j = 0; j < cnt; ++j) {
+        const float4 e = sbox[j];
+        if (__float_as_int(e.z) == want) {
+          const float dx = px - e.x, dy = py - e.y;
+          const float d = dx * dx + dy * dy;
+          if (best_row < 0 || d < best) { best = d; best_row = c0 + j; }
+        }
+      }
+    }
+  }
+  if (i < n) instance[i] = best_row >= 0 ? instances[best_row] : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -76,6 +143,21 @@ int pn_seg_point_labels(const float* seg_sample, int h, int w, int classes, cons
   PN_REQUIRE(grid_ind != nullptr, "seg_point_labels: null grid_ind");
   hipLaunchKernelGGL(seg_point_labels_kernel, dim3(pn::cdiv(n, 256)), dim3(256), 0, pn::S(stream), seg_sample, h, w, classes, grid_ind, n, labels);
   return pn::check_launch("seg_point_labels_kernel");
+}
+
+int pn_panoptic_points_f32(const float* seg_sample, int h, int w, int classes, int pixel_stride, const int64_t* grid_ind, int n, const float* points,
+                           int point_stride, int x_col, float cos_a, float sin_a, const float* boxes, int box_stride, const float* scores,
+                           const int64_t* box_labels, const int64_t* instances, int m, const int32_t* sem2box, float score_thr, int64_t* labels,
+                           int64_t* instance, pn_stream_t stream) {
+  PN_REQUIRE(h >= 1 && w >= 1 && classes >= 1 && pixel_stride >= classes && n >= 0 && m >= 0, "panoptic_points: bad arguments");
+  if (n == 0) return PN_OK;
+  PN_REQUIRE(seg_sample && grid_ind && points && sem2box && labels && instance, "panoptic_points: null pointer");
+  PN_REQUIRE(x_col >= 0 && point_stride >= x_col + 2, "panoptic_points: the point rows must hold columns x_col and x_col + 1");
+  PN_REQUIRE(m == 0 || (boxes && scores && box_labels && instances && box_stride >= 2), "panoptic_points: null box arrays or box_stride < 2");
+  hipLaunchKernelGGL(panoptic_points_kernel, dim3(pn::cdiv(n, kPanopticBlock)), dim3(kPanopticBlock), 0, pn::S(stream), seg_sample, h, w, classes,
+                     pixel_stride, grid_ind, n, points, point_stride, x_col, cos_a, sin_a, boxes, box_stride, scores, box_labels, instances, m, sem2box,
+                     score_thr, labels, instance);
+  return pn::check_launch("panoptic_points_kernel");
 }
 
 }  // extern "C"

@@ -242,8 +242,11 @@ class PolarStream(PointPillars):
     """PolarStream (det3d/models/detectors/polarstream.py:7-180): a sweep given as a LIST of azimuth-sector examples is processed
     sector by sector, the neck (RPNTECP / RPNBDCP) pads every sector with the context rows the previous sector left behind, and the
     per-sector detections are rotated back into the sweep's frame and concatenated (single_stage.py:83-165).  A single example (dict)
-    is the full-sweep case.  Eval mode; detection super-task; stateful NMS across sectors (test_cfg.stateful_nms, the default of the
-    reference's 4-sector configs) is supported, panoptic fusion is not."""
+    is the full-sweep case.  Eval mode; stateful NMS across sectors (test_cfg.stateful_nms, the default of the reference's 4-sector
+    configs) is supported.  With a segmentation head every sector also yields per-point semantic labels ('seg'), and with
+    test_cfg.panoptic per-point instance ids ('ins', polarstream.py:161-171): the boxes' ids are carried from sector to sector like
+    the stateful NMS's detections, and the merged detections keep their 'instances' (the reference drops them) so that 'ins' can be
+    mapped back to a box.  ``key_points_index`` reordering of the reference's merge_sectors is not built."""
 
     def forward_one_sector(self, example, return_loss=True, **kwargs):
         eval_only(self, "PolarStream")
@@ -263,14 +266,24 @@ class PolarStream(PointPillars):
             x2, nxt = self.neck.forward_nhwc(canvas, kwargs.get("prev_context", []), kwargs.get("sec_id", 0))
         else:                                   # plain RPN: no context, its own signature (return_blocks, pillars)
             x2 = self.neck.forward_nhwc(canvas)
-        preds = self.bbox_head(ops.as_nchw(x2))
+        if return_loss:
+            preds = self.bbox_head(ops.as_nchw(x2))
+        else:                                   # polarstream.py:149-152: the seg head (when there is one) on the sector canvas + the neck output
+            preds = self._heads(canvas, x2)
         ret = {}
         if return_loss:
             ret.update(self.bbox_head.loss(example, preds))
         elif kwargs.get("raw_preds", False) or self.test_cfg is None:
             ret.update(preds)
         else:
-            ret["det"] = self.bbox_head.predict(example, preds, self.test_cfg, sec_id=kwargs.get("sec_id", 0), prev_dets=kwargs.get("prev_dets"))
+            sec_id = kwargs.get("sec_id", 0)
+            ret["det"] = self.bbox_head.predict(example, preds, self.test_cfg, sec_id=sec_id, prev_dets=kwargs.get("prev_dets"))
+            if self.seg_head is not None:      # polarstream.py:163-171
+                if self._test_flag("panoptic"):
+                    self.seg_head.predict_panoptic(example, preds, self.test_cfg, ret, voxel_shape=self.bbox_head.voxel_shape,
+                                                   class_names=self.bbox_head.class_names, sec_id=sec_id)
+                else:
+                    ret["seg"] = self.seg_head.predict(example, preds, self.test_cfg)
         if len(nxt):
             ret["next_context"] = nxt
         return ret
@@ -278,29 +291,33 @@ class PolarStream(PointPillars):
     def forward(self, example, return_loss=True, **kwargs):
         if isinstance(example, dict):
             return self.forward_one_sector(example, return_loss, **kwargs)
-        get = (lambda k, d=None: self.test_cfg.get(k, d)) if hasattr(self.test_cfg, "get") else (lambda k, d=None: getattr(self.test_cfg, k, d))
-        if self.test_cfg is not None and get("panoptic", False):
-            raise NotImplementedError("PolarStream: panoptic fusion across sectors is not built")
-        stateful = self.test_cfg is not None and bool(get("stateful_nms", False))
+        stateful, panoptic = self._test_flag("stateful_nms"), self._test_flag("panoptic")
         rets, prev = [], []
         for i, ex in enumerate(example):
             kw = dict(kwargs, prev_context=prev, sec_id=i)
-            if stateful and i > 0 and "det" in rets[-1]:
+            if (stateful or panoptic) and i > 0 and "det" in rets[-1]:
                 kw["prev_dets"] = rets[-1]["det"]     # polarstream.py:91-92
             r = self.forward_one_sector(ex, return_loss, **kw)
             prev = r.pop("next_context", []) if i < len(example) - 1 else []
             r.pop("next_context", None)
             rets.append(r)
-        out = self.merge_sectors(rets, len(example[-1]["num_points"]), stateful)
-        if stateful and "det" in out:
+        out = self.merge_sectors(rets, len(example[-1]["num_points"]), stateful or panoptic)
+        if (stateful or panoptic) and "det" in out:
             for det, meta in zip(out["det"], example[-1].get("metadata", [None] * len(out["det"]))):
                 det["metadata"] = meta
         return out
 
+    def _test_flag(self, name) -> bool:
+        cfg = self.test_cfg
+        if cfg is None:
+            return False
+        return bool(cfg.get(name, False) if hasattr(cfg, "get") else getattr(cfg, name, False))
+
     def merge_sectors(self, sectors, batch_size, stateful=False):
         """single_stage.py:83-165 for the keys this build produces: losses are lists concatenated over sectors, detections are
-        concatenated per sample; with stateful NMS the LAST sector's per-task lists already hold the whole sweep (merge_dets
-        :137-153: tasks concatenated, labels offset by the preceding tasks' class counts)"""
+        concatenated per sample; with stateful NMS or panoptic fusion (``stateful``) the LAST sector's per-task lists already hold the
+        whole sweep (merge_dets :137-153: tasks concatenated, labels offset by the preceding tasks' class counts; 'instances', where the
+        lists carry them, are kept); 'seg' / 'ins' are concatenated per sample and token in sector order (:106-116)"""
         out = {}
         for k in sectors[0]:
             vals = [s[k] for s in sectors]
@@ -316,6 +333,8 @@ class PolarStream(PointPillars):
                         flag += ncls
                     merged.append(dict(box3d_lidar=torch.cat([t[i]["box3d_lidar"] for t in tasks]), scores=torch.cat([t[i]["scores"] for t in tasks]),
                                        label_preds=torch.cat(labels)))
+                    if all("instances" in t[i] for t in tasks):
+                        merged[-1]["instances"] = torch.cat([t[i]["instances"] for t in tasks])
                 out[k] = merged
             elif k == "det":
                 merged = []
@@ -325,8 +344,15 @@ class PolarStream(PointPillars):
                         d[f] = vals[0][i][f] if f == "metadata" else torch.cat([v[i][f] for v in vals])
                     merged.append(d)
                 out[k] = merged
-            elif k == "det_preds":
+            elif k in ("det_preds", "seg_preds"):
                 out[k] = vals
+            elif k in ("seg", "ins"):
+                merged = [{} for _ in range(batch_size)]
+                for sec in vals:
+                    for i in range(batch_size):
+                        for token, v in sec[i].items():
+                            merged[i].setdefault(token, []).append(v)
+                out[k] = [{token: torch.cat(v) for token, v in m.items()} for m in merged]
         return out
 
 
@@ -376,6 +402,8 @@ class PolarStreamBDCP(PolarStream):
         eval_only(self, "PolarStreamBDCP")
         if return_loss:
             raise NotImplementedError("PolarStreamBDCP: training (the two-sweep loss path) is not built")
+        if self._test_flag("panoptic"):
+            raise NotImplementedError("PolarStreamBDCP: test_cfg.panoptic (polarstream.py:423-460) is not built; PolarStream has it")
         canvas, batch = self._canvas(example)
         nsec = self.nsectors
         bs = batch // nsec

@@ -80,6 +80,39 @@ def _conv_bias(conv: nn.Conv2d, act, **kw) -> ops.ConvLayer:
                          act=act, **kw)
 
 
+def panoptic_instance_ids(out_cells: torch.Tensor, cells: int, prev_instances, prev_count: int, sec_id: int, stateful: bool) -> torch.Tensor:
+    """Instance ids (int64) of one sample's detection list under test_cfg.panoptic (post_processing, center_head.py:502-509, 552-573).
+    Index bookkeeping only: runs on whatever device its tensors live on.
+
+    out_cells: the (n,) cell indices of the boxes this sector's NMS kept, in output order; ``cells`` = h * w of the head map;
+    prev_instances: the ids of the previous sectors' list (None or empty: there is none), prev_count its length.
+    * sector 0: arange(n) -- the ids start at 0, which is also "no instance" in the per-point output (the reference's behaviour).
+    * stateful NMS, later sector: the output list is the NMS over [previous list, this sector].  A carried-over box
+      (out_cells >= cells, row out_cells - cells of the previous list) keeps its id; this sector's survivors get offset + k, k counting
+      them in output order.  offset = prev_count + 1 as in the reference (:509) while that is above every id in the previous list,
+      which holds as long as no carried-over box was ever dropped; once the NMS has dropped one (suppressed, or cut by
+      nms_post_max_size) the reference's offset runs into ids still in use, so offset = max(prev_count, max(prev_instances)) + 1:
+      the ids of a list never repeat.  (The id of a box that has left the list may be issued again later.)  -> (n,) ids
+    * no stateful NMS, later sector: the output list is the previous list followed by this sector's n boxes, ids
+      [prev_instances, prev_count + arange(n)].  -> (prev_count + n,) ids"""
+    n = int(out_cells.shape[0])
+    dev = out_cells.device
+    new = torch.arange(n, dtype=torch.int64, device=dev)
+    if sec_id == 0:
+        return new
+    prev = torch.zeros((0,), dtype=torch.int64, device=dev) if prev_instances is None else prev_instances.to(dev).to(torch.int64)
+    assert int(prev.shape[0]) == int(prev_count), "the previous list's ids and its length differ"
+    if not stateful:
+        return torch.cat([prev, new + prev_count])
+    carried = out_cells >= cells
+    ids = torch.zeros((n,), dtype=torch.int64, device=dev)
+    ids[carried] = prev[(out_cells[carried] - cells).to(torch.int64)]
+    fresh = ~carried
+    offset = prev.max().clamp(min=prev_count) + 1 if prev_count else 1
+    ids[fresh] = torch.arange(int(fresh.sum()), dtype=torch.int64, device=dev) + offset
+    return ids
+
+
 @BBOX_HEADS.register_module
 class CenterHead(nn.Module):
     """Plain CenterPoint head: shared 3x3 conv + ReLU, then per task / per head
@@ -180,21 +213,24 @@ class CenterHead(nn.Module):
         """decode + rotated NMS on the device (center_head.py:404-460, 350-402, 462-577): the multi-class rotate_nms_pcdet path and
         the per-class one (test_cfg.per_class_nms, batched_nms_rotated); test_cfg.double_flip merges groups of four flipped copies first
         (center_head.py:289-346, 425-427), test_cfg.stateful_nms lets the previous sectors' detections (kwargs prev_dets / sec_id) compete
-        (center_head.py:466, 486-509); panoptic fusion raises NotImplementedError (segmentation is out of scope).  Returns the reference's list (one dict per sample) of
-        'box3d_lidar' (n, 9|7), 'scores', 'label_preds', 'metadata'."""
+        (center_head.py:466, 486-509).  Returns the reference's list (one dict per sample) of 'box3d_lidar' (n, 9|7), 'scores',
+        'label_preds', 'metadata'.  test_cfg.panoptic (center_head.py:502-509, 552-573) adds 'instances' (int64, one id per box; the
+        bookkeeping is ``panoptic_instance_ids``) and, like stateful NMS, returns the per-task lists unmerged (:438-439), the next
+        sector's prev_dets: without stateful NMS a later sector's list is then the previous list followed by the sector's own boxes."""
         import ctypes as C
         lib = hip.load()
         get = (lambda k, d=None: test_cfg.get(k, d)) if hasattr(test_cfg, "get") else (lambda k, d=None: getattr(test_cfg, k, d))
-        if get("panoptic", False):
-            raise NotImplementedError("predict: test_cfg.panoptic (instance ids for the segmentation super-task) is not built")
+        panoptic = bool(get("panoptic", False))         # center_head.py:467, 502-509, 552-573
         double_flip = bool(get("double_flip", False))   # center_head.py:412, 425-427
         stateful = bool(get("stateful_nms", False))     # center_head.py:466, 486-501, 507-509
         if stateful and (double_flip or kwargs.get("device_only", False)):
             raise NotImplementedError("predict: stateful NMS is not combined with double flip / device_only outputs")
+        if panoptic and (double_flip or kwargs.get("device_only", False)):
+            raise NotImplementedError("predict: test_cfg.panoptic is not combined with double flip / device_only outputs")
         per_class = bool(get("per_class_nms", False))   # batched_nms_rotated of the nuScenes configs (center_head.py:514-518)
         if kwargs.get("device_only", False) and len(preds_dicts["det_preds"]) != 1:
             raise NotImplementedError("predict(device_only=True) supports a single task")
-        prev_dets = kwargs.get("prev_dets") if stateful else None
+        prev_dets = kwargs.get("prev_dets") if (stateful or panoptic) else None
         sec_id = int(kwargs.get("sec_id", 0))
         nms = get("nms")
         nget = (lambda k: nms[k]) if isinstance(nms, dict) else (lambda k: getattr(nms, k))
@@ -284,6 +320,10 @@ class CenterHead(nn.Module):
                 counts = out_count.cpu().tolist()
                 rets.append([dict(box3d_lidar=out_boxes[i, :n], scores=out_scores[i, :n], label_preds=out_labels[i, :n], cells=out_cells[i, :n])
                              for i, n in enumerate(counts)])
+                if panoptic:
+                    for i, d in enumerate(rets[-1]):
+                        pi = prev[i]["instances"] if pcap else None
+                        d["instances"] = panoptic_instance_ids(d["cells"], h * w, pi, 0 if pi is None else int(pi.numel()), sec_id, True)
                 continue
             hip.call(decode_fn, hm.data_ptr(), hm.stride(3), ncls, pd["reg"].data_ptr(), pd["reg"].stride(3),
                      pd["height"].data_ptr(), pd["height"].stride(3), pd["dim"].data_ptr(), pd["dim"].stride(3), pd["rot"].data_ptr(),
@@ -302,8 +342,18 @@ class CenterHead(nn.Module):
             counts = out_count.cpu().tolist()  # the one host sync of the call: the API returns exact-size tensors
             rets.append([dict(box3d_lidar=out_boxes[i, :n], scores=out_scores[i, :n], label_preds=out_labels[i, :n], cells=out_cells[i, :n])
                          for i, n in enumerate(counts)])
-        if stateful:
-            return rets   # per task, per sample, unmerged: the next sector's prev_dets (center_head.py:439-440)
+            if panoptic:
+                # the sweep's list so far = the previous sectors' list followed by this sector's (rotated) boxes (center_head.py:562-571);
+                # 'cells' stay each sector's own cell indices
+                prev = None if (prev_dets is None or sec_id == 0) else prev_dets[task_id]
+                for i, d in enumerate(rets[-1]):
+                    pi = None if prev is None else prev[i]["instances"]
+                    d["instances"] = panoptic_instance_ids(d["cells"], h * w, pi, 0 if pi is None else int(pi.numel()), sec_id, False)
+                    if pi is not None and pi.numel():
+                        for k in ("box3d_lidar", "scores", "label_preds", "cells"):
+                            d[k] = torch.cat([prev[i][k], d[k]])
+        if stateful or panoptic:
+            return rets   # per task, per sample, unmerged: the next sector's prev_dets (center_head.py:438-440)
         metas = example.get("metadata", [None] * len(rets[0])) if isinstance(example, dict) else [None] * len(rets[0])
         if double_flip:
             metas = list(metas)[::4] if len(metas) >= 4 * len(rets[0]) else metas   # meta_list[:4 * batch:4]

@@ -1,8 +1,10 @@
 """Segmentation head of the reference's nuScenes polar config (`super_tasks = ['det', 'seg']`): SingleConvHead
-(det3d/models/seg_heads/seg_head.py:53-83, 176-195) and its loss object SegLoss (det3d/models/losses/seg_loss.py:8-22).
-Secondary to the detection hot path: forward and per-point prediction run on the HIP kernels (eval); the loss (Lovasz softmax +
-cross entropy) is not built."""
+(det3d/models/seg_heads/seg_head.py:53-83, 99-168, 176-195) and its loss object SegLoss (det3d/models/losses/seg_loss.py:8-22).
+Secondary to the detection hot path: forward, per-point prediction and the panoptic fusion with the detection boxes run on the HIP
+kernels (eval); the loss (Lovasz softmax + cross entropy) is not built."""
 from __future__ import annotations
+
+import math
 
 import torch
 from torch import nn
@@ -10,6 +12,10 @@ from torch import nn
 from . import builder, hip, ops
 from .builder import LOSSES, SEG_HEAD
 from .nn_utils import PlanCache, eval_only
+
+# the ten nuScenes lidarseg thing classes in label order (semantic labels 1..10) under their detection class names
+# (the module constant `semantic2box`, seg_head.py:11-22)
+SEMANTIC2BOX = ["barrier", "bicycle", "bus", "car", "construction_vehicle", "motorcycle", "pedestrian", "traffic_cone", "trailer", "truck"]
 
 
 @LOSSES.register_module
@@ -95,3 +101,76 @@ class SingleConvHead(nn.Module):
             token = meta["token"] if isinstance(meta, dict) and "token" in meta else i
             out.append({token: labels})
         return out
+
+    @torch.no_grad()
+    def predict_panoptic(self, example, preds_dicts, test_cfg, ret_dict, *, voxel_shape, class_names, sec_id, semantic2box=None, score_thr=0.3):
+        """panoptic fusion (seg_head.py:99-168): the per-point semantic labels of ``predict`` plus, for every point, the instance id of
+        the nearest box centre of its class, one launch per sample (`pn_panoptic_points_f32`).  Fills ``ret_dict['seg']`` and
+        ``ret_dict['ins']`` (lists of {token: (n_i,) int64}; the reference wraps them in iterators) and returns ``ret_dict``.
+
+        ``ret_dict['det']`` holds the per-task lists of ``CenterHead.predict`` under ``test_cfg.panoptic`` (with 'instances'); as in
+        the reference only the FIRST task's boxes are used (``ret_dict['det'][0]``, "only works for single group head").  Semantic
+        labels 1..len(semantic2box) are thing classes: label k maps to the box class named ``semantic2box[k - 1]``, whose position in
+        the flattened ``class_names`` is the box label (ValueError when the name is missing).  Eligible boxes have that label and
+        score > ``score_thr``; the point's Cartesian (x, y) -- columns 3:5 of a polar point row (``voxel_shape='cylinder'``), 0:2
+        otherwise -- is rotated by the sector angle (``interval * sec_id``; cuboid: ``2 pi / interval * sec_id``) first.  Stuff points
+        and things without an eligible box get 0 -- which is also the id of the sweep's first box (the reference's ids start at 0)."""
+        seg = preds_dicts["seg_preds"]
+        hip.require_device(seg)
+        assert seg.dim() == 4 and seg.stride(1) == 1, "seg_preds must be the channels-last view produced by forward"
+        bsz, ncls, h, w = seg.shape
+        dev = seg.device
+        names = [n for sub in class_names for n in ([sub] if isinstance(sub, str) else sub)]
+        things = SEMANTIC2BOX if semantic2box is None else list(semantic2box)
+        table = [-1] * (ncls + 1)
+        for k, name in enumerate(things[:ncls]):
+            if name not in names:
+                raise ValueError(f"predict_panoptic: semantic label {k + 1} maps to the box class '{name}', which is not among the head's class_names {names}")
+            table[k + 1] = names.index(name)
+        sem2box = torch.tensor(table, dtype=torch.int32, device=dev)
+        sec_id = int(sec_id)
+        angle = 0.0
+        if sec_id > 0:
+            interval = float(test_cfg.get("interval") if hasattr(test_cfg, "get") else getattr(test_cfg, "interval"))
+            angle = interval * sec_id if voxel_shape == "cylinder" else 2 * math.pi / interval * sec_id
+        x_col = 3 if voxel_shape == "cylinder" else 0
+        points = example["points"]
+        hip.require_device(points)
+        assert points.dim() == 2 and points.dtype == torch.float32 and points.shape[1] >= x_col + 2
+        if points.numel() and points.stride(1) != 1:
+            points = points.contiguous()
+        point_stride = points.stride(0) if points.shape[0] > 1 else points.shape[1]      # (the stride of a 0- or 1-row tensor is arbitrary)
+        num = example["num_points"]
+        num = [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
+        assert len(num) == bsz and sum(num) <= points.shape[0], "num_points does not match the batch / the point list"
+        dets = ret_dict["det"][0]
+        ret_dict["seg"], ret_dict["ins"] = [], []
+        start = 0
+        for i in range(bsz):
+            gi = example["valid_grid_ind"][i]
+            gi = (gi if torch.is_tensor(gi) else torch.as_tensor(gi)).to(dev).to(torch.int64).contiguous()
+            n = int(gi.shape[0])
+            assert gi.dim() == 2 and gi.shape[1] == 3 and n == num[i], "valid_grid_ind[i] must hold one [z, y, x] row per point of sample i"
+            det = dets[i]
+            boxes, scores = det["box3d_lidar"].float(), det["scores"].float().contiguous()
+            box_labels, ids = det["label_preds"].to(torch.int64).contiguous(), det["instances"].to(torch.int64).contiguous()
+            hip.require_device(boxes, scores, box_labels, ids)
+            if boxes.stride(1) != 1:
+                boxes = boxes.contiguous()
+            m = int(scores.shape[0])
+            assert boxes.shape[0] == m and box_labels.shape[0] == m and ids.shape[0] == m, "the sample's boxes, scores, labels and instances differ in length"
+            labels = torch.empty((n,), dtype=torch.int64, device=dev)
+            ins = torch.empty((n,), dtype=torch.int64, device=dev)
+            base = seg[i].permute(1, 2, 0)                       # (H, W, ncls) view of the (possibly channel-padded) NHWC buffer, read in place
+            assert base.stride(2) == 1 and base.stride(0) == w * base.stride(1)
+            rows = points[start:start + n]
+            hip.call("pn_panoptic_points_f32", base.data_ptr(), h, w, ncls, base.stride(1), gi.data_ptr(), n, rows.data_ptr(), point_stride, x_col,
+                     math.cos(angle), math.sin(angle), boxes.data_ptr() if m else None, boxes.stride(0) if m else 2, scores.data_ptr() if m else None,
+                     box_labels.data_ptr() if m else None, ids.data_ptr() if m else None, m, sem2box.data_ptr(), float(score_thr), labels.data_ptr(),
+                     ins.data_ptr(), hip.stream())
+            start += n
+            meta = example["metadata"][i]
+            token = meta["token"] if isinstance(meta, dict) and "token" in meta else i
+            ret_dict["seg"].append({token: labels})
+            ret_dict["ins"].append({token: ins})
+        return ret_dict
