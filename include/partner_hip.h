@@ -837,6 +837,21 @@ int pn_panoptic_points_f32(const float *seg_sample, int h, int w, int classes, i
                            const float *points, int point_stride, int x_col, float cos_a, float sin_a, const float *boxes,
                            int box_stride, const float *scores, const int64_t *box_labels, const int64_t *instances, int m,
                            const int32_t *sem2box, float score_thr, int64_t *labels, int64_t *instance, pn_stream_t stream);
+/* pn_panoptic_points_f32 for ALL samples of a sector in one launch, every count read from device memory
+ * (SingleConvHead.predict_panoptic(device_only=True); seg_head.py:99-168, the per-sample loop of :118-166): sample b's logits start
+ * at seg + b * sample_stride floats, its point rows are [offsets[b], offsets[b + 1]) of the flat grid_ind / points / labels /
+ * instance arrays (offsets: DEVICE int32[batch + 1], clamped to [0, n_total]; n_total = rows of the flat arrays, which sizes the grid),
+ * its boxes the first count[b] (DEVICE int32[batch]) rows of the (batch, capacity, .) detection list of
+ * CenterHead.predict(device_only=True): boxes with box_stride floats per row, scores, box_labels, instances.  Same arithmetic per
+ * point, bit for bit; rows at or past count[b] are never read as boxes.  boxes == NULL: labels only (seg_head.py:176-195; points,
+ * the box arrays, sem2box and instance may then be NULL). */
+int pn_panoptic_points_batched_f32(const float *seg, long long sample_stride, int batch, int h, int w, int classes,
+                                   int pixel_stride, const int64_t *grid_ind, const int32_t *offsets, int n_total,
+                                   const float *points, int point_stride, int x_col, float cos_a, float sin_a,
+                                   const float *boxes, int box_stride, int capacity, const float *scores,
+                                   const int64_t *box_labels, const int64_t *instances, const int32_t *count,
+                                   const int32_t *sem2box, float score_thr, int64_t *labels, int64_t *instance,
+                                   pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * next-1  sparse 3-D convolutions of the middle encoder SpMiddleResNetFHD
@@ -1014,6 +1029,28 @@ int pn_swv_set_criterion_f32(const float *hm, int hm_ps, int ncls, const float *
  * rotated by +angle, heading -= angle; boxes (batch, capacity, box_dims) with counts (batch) valid rows each */
 int pn_rotate_boxes_f32(float *boxes, const int32_t *counts, int batch, int capacity, int box_dims, double angle,
                         pn_stream_t stream);
+
+/* Device-resident detection lists of a streamed sweep (CenterHead.predict(device_only=True) under test_cfg.stateful_nms /
+ * test_cfg.panoptic): (batch, capacity, .) buffers with a DEVICE count per sample, rows at or past the count unspecified.
+ * pn_det_list_append: the sweep's list so far without stateful NMS = the previous list followed by this sector's rotated boxes
+ * (post_processing, center_head.py:562-571): rows [0, count[b]) of the sector's outputs are copied behind row prev_count[b] of the
+ * out_capacity-row buffers (out_capacity >= prev_capacity + capacity), out_count = prev_count + count.  prev_capacity == 0: no
+ * previous list (its pointers may be NULL).  The outputs must not alias the inputs. */
+int pn_det_list_append(const float *prev_boxes, const float *prev_scores, const int64_t *prev_labels,
+                       const int32_t *prev_cells, const int32_t *prev_count, int prev_capacity, const float *boxes,
+                       const float *scores, const int64_t *labels, const int32_t *cells, const int32_t *count,
+                       int capacity, int batch, int box_dims, float *out_boxes, float *out_scores, int64_t *out_labels,
+                       int32_t *out_cells, int32_t *out_count, int out_capacity, pn_stream_t stream);
+/* The boxes' instance ids under test_cfg.panoptic (post_processing, center_head.py:502-509, 552-573; the rules are stated and
+ * CPU-tested in heads.panoptic_instance_ids), one block per sample, ids (batch, capacity) int64, rows [0, count[b]) written.
+ * sec_id == 0: ids[k] = k.  stateful != 0, later sector: a row with cells >= map_cells (carried over by the stateful NMS) takes
+ * prev_ids[cells - map_cells], a fresh row offset + its rank among the fresh rows in output order, offset =
+ * max(prev_count, max(prev_ids[:prev_count])) + 1 (1 for an empty previous list).  stateful == 0, later sector (cells, count: the
+ * appended list of pn_det_list_append): rows [0, prev_count) keep prev_ids, row k >= prev_count gets k.  prev_ids (batch,
+ * prev_capacity) int64, prev_count DEVICE int32[batch]; prev_capacity == 0: no previous list. */
+int pn_panoptic_box_ids(const int32_t *cells, const int32_t *count, int batch, int capacity, int map_cells,
+                        const int64_t *prev_ids, const int32_t *prev_count, int prev_capacity, int sec_id, int stateful,
+                        int64_t *ids, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Sector streaming (a sweep processed as azimuth sectors, one after the other).

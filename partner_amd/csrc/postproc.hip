@@ -725,6 +725,119 @@ __global__ void rotate_boxes_kernel(float* __restrict__ boxes, const int32_t* __
 }
 }  // namespace
 
+namespace {
+// Device-resident detection lists of a streamed sweep (CenterHead.predict(device_only=True)): fixed-capacity (B, cap, .) buffers with a
+// device count per sample, handed from sector to sector without a readback.
+struct AppendArgs {
+  const float* pb; const float* ps; const int64_t* pl; const int32_t* pcell; const int32_t* pc; int pcap;      // the previous sectors' list
+  const float* sb; const float* ss; const int64_t* sl; const int32_t* scell; const int32_t* sc; int scap;      // this sector's (rotated) boxes
+  float* ob; float* os; int64_t* ol; int32_t* ocell; int32_t* oc; int ocap;
+  int nb;
+};
+// the sweep's list so far = the previous list followed by this sector's boxes (center_head.py:562-571); one lane per output row
+__global__ void det_list_append_kernel(AppendArgs a) {
+  const int b = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+  const int pc = a.pcap > 0 ? min(max(a.pc[b], 0), a.pcap) : 0;
+  const int total = min(pc + min(max(a.sc[b], 0), a.scap), a.ocap);
+  if (k == 0) a.oc[b] = total;
+  if (k >= total) return;
+  const bool old = k < pc;
+  const size_t src = old ? (size_t)b * a.pcap + k : (size_t)b * a.scap + (k - pc);
+  const size_t dst = (size_t)b * a.ocap + k;
+  const float* from = (old ? a.pb : a.sb) + src * a.nb;
+  for (int c = 0; c < a.nb; ++c) a.ob[dst * a.nb + c] = from[c];
+  a.os[dst] = old ? a.ps[src] : a.ss[src];
+  a.ol[dst] = old ? a.pl[src] : a.sl[src];
+  a.ocell[dst] = old ? a.pcell[src] : a.scell[src];
+}
+
+// Instance ids of the boxes of a detection list under test_cfg.panoptic: the rules of heads.panoptic_instance_ids (post_processing,
+// center_head.py:502-509, 552-573) with every count read from device memory.  One block per sample.  Stateful NMS, later sector: a
+// carried-over row (cells >= hw) keeps prev_ids[cells - hw]; a fresh row takes offset + its rank among the fresh rows in output order
+// -- a block prefix scan, 256 rows per step: wave ballots, the four wave totals through LDS, a running base --, offset =
+// max(prev_count, max(prev_ids[:prev_count])) + 1, or 1 for an empty previous list.
+constexpr int kIdsBlock = 256;
+__global__ __launch_bounds__(kIdsBlock) void panoptic_box_ids_kernel(const int32_t* __restrict__ cells, const int32_t* __restrict__ count, int cap, int hw,
+                                                                     const int64_t* __restrict__ prev_ids, const int32_t* __restrict__ prev_count,
+                                                                     int prev_cap, int sec_id, int stateful, int64_t* __restrict__ ids) {
+  __shared__ long long wave_max[kIdsBlock / 64];
+  __shared__ int wave_cnt[kIdsBlock / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n = min(max(count[b], 0), cap);
+  const int32_t* cs = cells + (size_t)b * cap;
+  int64_t* out = ids + (size_t)b * cap;
+  if (sec_id == 0) {
+    for (int k = tid; k < n; k += kIdsBlock) out[k] = k;
+    return;
+  }
+  const int pc = prev_cap > 0 ? min(max(prev_count[b], 0), prev_cap) : 0;
+  const int64_t* pid = prev_cap > 0 ? prev_ids + (size_t)b * prev_cap : nullptr;
+  if (!stateful) {      // the previous list followed by this sector's boxes: row prev_count + k gets prev_count + k
+    for (int k = tid; k < n; k += kIdsBlock) out[k] = k < pc ? pid[k] : (int64_t)k;
+    return;
+  }
+  long long mx = pc;
+  for (int k = tid; k < pc; k += kIdsBlock) mx = max(mx, (long long)pid[k]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (long long)__shfl_xor(mx, o, 64));
+  if (lane == 0) wave_max[wv] = mx;
+  __syncthreads();
+  mx = wave_max[0];
+  for (int k = 1; k < kIdsBlock / 64; ++k) mx = max(mx, wave_max[k]);
+  const long long offset = pc ? mx + 1 : 1;
+  int base = 0;      // fresh rows before this step
+  for (int c0 = 0; c0 < n; c0 += kIdsBlock) {      // n is uniform across the block: so are the barriers
+    const int k = c0 + tid;
+    const bool live = k < n;
+    const int cell = live ? cs[k] : 0;
+    const bool fresh = live && cell < hw;
+    const unsigned long long vote = __ballot(fresh);
+    const int before = __popcll(vote & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_cnt[wv] = __popcll(vote);
+    __syncthreads();
+    int pre = 0, tot = 0;
+    for (int v = 0; v < kIdsBlock / 64; ++v) {
+      if (v < wv) pre += wave_cnt[v];
+      tot += wave_cnt[v];
+    }
+    if (live) {
+      const int r = cell - hw;      // row of a carried-over box in the previous list
+      out[k] = fresh ? offset + base + pre + before : (r < pc ? pid[r] : 0);
+    }
+    base += tot;
+    __syncthreads();      // wave_cnt is rewritten by the next step
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int pn_det_list_append(const float* prev_boxes, const float* prev_scores, const int64_t* prev_labels, const int32_t* prev_cells,
+                       const int32_t* prev_count, int prev_capacity, const float* boxes, const float* scores, const int64_t* labels,
+                       const int32_t* cells, const int32_t* count, int capacity, int batch, int box_dims, float* out_boxes, float* out_scores,
+                       int64_t* out_labels, int32_t* out_cells, int32_t* out_count, int out_capacity, pn_stream_t stream) {
+  PN_REQUIRE(boxes && scores && labels && cells && count && out_boxes && out_scores && out_labels && out_cells && out_count, "det_list_append: null pointer");
+  PN_REQUIRE(prev_capacity == 0 || (prev_boxes && prev_scores && prev_labels && prev_cells && prev_count), "det_list_append: previous list missing");
+  PN_REQUIRE(batch >= 1 && batch <= 65535 && box_dims >= 1 && prev_capacity >= 0 && capacity >= 1 && out_capacity >= prev_capacity + capacity,
+             "det_list_append: bad sizes (out_capacity must hold both lists)");
+  PN_REQUIRE(out_boxes != boxes && out_boxes != prev_boxes && out_count != count && out_count != prev_count, "det_list_append: the output must not alias an input");
+  AppendArgs a{prev_boxes, prev_scores, prev_labels, prev_cells, prev_count, prev_capacity, boxes, scores, labels, cells, count, capacity,
+               out_boxes, out_scores, out_labels, out_cells, out_count, out_capacity, box_dims};
+  hipLaunchKernelGGL(det_list_append_kernel, dim3(pn::cdiv(out_capacity, 256), batch), dim3(256), 0, pn::S(stream), a);
+  return pn::check_launch("det_list_append_kernel");
+}
+
+int pn_panoptic_box_ids(const int32_t* cells, const int32_t* count, int batch, int capacity, int map_cells, const int64_t* prev_ids,
+                        const int32_t* prev_count, int prev_capacity, int sec_id, int stateful, int64_t* ids, pn_stream_t stream) {
+  PN_REQUIRE(cells && count && ids && batch >= 1 && capacity >= 1 && map_cells >= 1 && sec_id >= 0 && prev_capacity >= 0, "panoptic_box_ids: bad arguments");
+  PN_REQUIRE(sec_id == 0 || prev_capacity == 0 || (prev_ids && prev_count), "panoptic_box_ids: previous ids missing");
+  hipLaunchKernelGGL(panoptic_box_ids_kernel, dim3(batch), dim3(kIdsBlock), 0, pn::S(stream), cells, count, capacity, map_cells, prev_ids, prev_count,
+                     prev_capacity, sec_id, stateful != 0, ids);
+  return pn::check_launch("panoptic_box_ids_kernel");
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int pn_rotate_boxes_f32(float* boxes, const int32_t* counts, int batch, int capacity, int box_dims, double angle, pn_stream_t stream) {

@@ -123,6 +123,85 @@ __global__ __launch_bounds__(kPanopticBlock) void panoptic_points_kernel(
   if (i < n) instance[i] = best_row >= 0 ? instances[best_row] : 0;
 }
 
+// The panoptic fusion of ALL samples of a sector in one launch (SingleConvHead.predict_panoptic(device_only=True)): the per-lane
+// arithmetic of panoptic_points_kernel, unchanged -- gather, argmax, rotation, chunked LDS box scan with strict '<' -- with every
+// count read from device memory, so that a streamed sweep never goes to the host.  blockIdx.y = sample; its point rows are
+// [offsets[b], offsets[b + 1]) of the flat arrays, its boxes the first count[b] rows of the (B, cap, .) detection list.  The grid's x
+// extent covers the flat row count (the host knows no sample's own): blocks past a sample's point count leave before the first
+// barrier, and count[b] is uniform across a block, so the barriers of the box scan stay legal.  kBoxes = false: labels only.
+struct PanopticBatch {
+  const float* seg; long long sample_stride; int H, W, C, pixel_stride;
+  const int64_t* grid_ind; const int32_t* offsets; int n_total;
+  const float* points; int point_stride, x_col; float cos_a, sin_a;
+  const float* boxes; int box_stride, cap;
+  const float* scores; const int64_t* box_labels; const int64_t* instances; const int32_t* count;
+  const int32_t* sem2box; float score_thr;
+  int64_t* labels; int64_t* instance;
+};
+
+template <bool kBoxes>
+__global__ __launch_bounds__(kPanopticBlock) void panoptic_points_batched_kernel(PanopticBatch a) {
+  __shared__ float4 sbox[kBoxes ? kPanopticChunk : 1];
+  const int b = blockIdx.y;
+  const int lo = min(max(a.offsets[b], 0), a.n_total), hi = min(max(a.offsets[b + 1], lo), a.n_total);
+  const int n = hi - lo;
+  if ((int)blockIdx.x * kPanopticBlock >= n) return;      // the whole block: no barrier has been reached
+  const int i = blockIdx.x * kPanopticBlock + threadIdx.x;
+  const size_t row = (size_t)lo + i;
+  int want = -1;
+  float px = 0.f, py = 0.f;
+  if (i < n) {
+    const int64_t y = a.grid_ind[row * 3 + 1], x = a.grid_ind[row * 3 + 2];
+    int lab = 0;
+    if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
+      const float* p = a.seg + (size_t)b * a.sample_stride + ((size_t)y * a.W + x) * a.pixel_stride;
+      float top = p[0];
+      int arg = 0;
+      for (int c = 1; c < a.C; ++c)
+        if (p[c] > top) { top = p[c]; arg = c; }
+      lab = arg + 1;
+      if (kBoxes) want = a.sem2box[lab];
+    }
+    a.labels[row] = lab;
+    if (kBoxes && want >= 0) {
+      const float* q = a.points + row * a.point_stride + a.x_col;
+      const float qx = q[0], qy = q[1];
+      px = qx * a.cos_a - qy * a.sin_a;
+      py = qx * a.sin_a + qy * a.cos_a;
+    }
+  }
+  if (!kBoxes) return;
+  const int m = min(max(a.count[b], 0), a.cap);
+  const float* boxes = a.boxes + (size_t)b * a.cap * a.box_stride;
+  const float* scores = a.scores + (size_t)b * a.cap;
+  const int64_t* box_labels = a.box_labels + (size_t)b * a.cap;
+  const int64_t* instances = a.instances + (size_t)b * a.cap;
+  float best = 0.f;
+  int best_row = -1;
+  for (int c0 = 0; c0 < m; c0 += kPanopticChunk) {
+    const int cnt = min(kPanopticChunk, m - c0);
+    if (c0) __syncthreads();      // every lane is done with the previous chunk
+    for (int j = threadIdx.x; j < cnt; j += kPanopticBlock) {
+      const size_t r = (size_t)(c0 + j);
+      const int64_t bl = box_labels[r];
+      const int lab = (scores[r] > a.score_thr && bl >= 0 && bl <= 0x7fffffff) ? (int)bl : -1;
+      sbox[j] = make_float4(boxes[r * a.box_stride], boxes[r * a.box_stride + 1], __int_as_float(lab), 0.f);
+    }
+    __syncthreads();
+    if (want >= 0) {
+      for (int j = 0; j < cnt; ++j) {
+        const float4 e = sbox[j];
+        if (__float_as_int(e.z) == want) {
+          const float dx = px - e.x, dy = py - e.y;
+          const float d = dx * dx + dy * dy;
+          if (best_row < 0 || d < best) { best = d; best_row = c0 + j; }
+        }
+      }
+    }
+  }
+  if (i < n) a.instance[row] = best_row >= 0 ? instances[best_row] : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -158,6 +237,33 @@ int pn_panoptic_points_f32(const float* seg_sample, int h, int w, int classes, i
                      pixel_stride, grid_ind, n, points, point_stride, x_col, cos_a, sin_a, boxes, box_stride, scores, box_labels, instances, m, sem2box,
                      score_thr, labels, instance);
   return pn::check_launch("panoptic_points_kernel");
+}
+
+int pn_panoptic_points_batched_f32(const float* seg, long long sample_stride, int batch, int h, int w, int classes, int pixel_stride,
+                                   const int64_t* grid_ind, const int32_t* offsets, int n_total, const float* points, int point_stride, int x_col,
+                                   float cos_a, float sin_a, const float* boxes, int box_stride, int capacity, const float* scores,
+                                   const int64_t* box_labels, const int64_t* instances, const int32_t* count, const int32_t* sem2box, float score_thr,
+                                   int64_t* labels, int64_t* instance, pn_stream_t stream) {
+  PN_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && classes >= 1 && pixel_stride >= classes && n_total >= 0 && sample_stride >= 0,
+             "panoptic_points_batched: bad arguments");
+  if (n_total == 0) return PN_OK;
+  PN_REQUIRE(seg && grid_ind && offsets && labels, "panoptic_points_batched: null pointer");
+  PanopticBatch a{};
+  a.seg = seg; a.sample_stride = sample_stride; a.H = h; a.W = w; a.C = classes; a.pixel_stride = pixel_stride;
+  a.grid_ind = grid_ind; a.offsets = offsets; a.n_total = n_total; a.labels = labels;
+  const dim3 grid(pn::cdiv(n_total, kPanopticBlock), batch);
+  if (!boxes) {      // labels only (SingleConvHead.predict(device_only=True))
+    hipLaunchKernelGGL(panoptic_points_batched_kernel<false>, grid, dim3(kPanopticBlock), 0, pn::S(stream), a);
+    return pn::check_launch("panoptic_points_batched_kernel<labels>");
+  }
+  PN_REQUIRE(points && sem2box && instance && scores && box_labels && instances && count, "panoptic_points_batched: null pointer");
+  PN_REQUIRE(x_col >= 0 && point_stride >= x_col + 2, "panoptic_points_batched: the point rows must hold columns x_col and x_col + 1");
+  PN_REQUIRE(capacity >= 1 && box_stride >= 2, "panoptic_points_batched: capacity < 1 or box_stride < 2");
+  a.points = points; a.point_stride = point_stride; a.x_col = x_col; a.cos_a = cos_a; a.sin_a = sin_a;
+  a.boxes = boxes; a.box_stride = box_stride; a.cap = capacity; a.scores = scores; a.box_labels = box_labels; a.instances = instances; a.count = count;
+  a.sem2box = sem2box; a.score_thr = score_thr; a.instance = instance;
+  hipLaunchKernelGGL(panoptic_points_batched_kernel<true>, grid, dim3(kPanopticBlock), 0, pn::S(stream), a);
+  return pn::check_launch("panoptic_points_batched_kernel");
 }
 
 }  // extern "C"

@@ -277,21 +277,42 @@ class PolarStream(PointPillars):
             ret.update(preds)
         else:
             sec_id = kwargs.get("sec_id", 0)
-            ret["det"] = self.bbox_head.predict(example, preds, self.test_cfg, sec_id=sec_id, prev_dets=kwargs.get("prev_dets"))
+            dev_only = bool(kwargs.get("device_only", False))      # device lists / flat per-point outputs: no readback (``forward``)
+            ret["det"] = self.bbox_head.predict(example, preds, self.test_cfg, sec_id=sec_id, prev_dets=kwargs.get("prev_dets"), device_only=dev_only)
             if self.seg_head is not None:      # polarstream.py:163-171
                 if self._test_flag("panoptic"):
                     self.seg_head.predict_panoptic(example, preds, self.test_cfg, ret, voxel_shape=self.bbox_head.voxel_shape,
-                                                   class_names=self.bbox_head.class_names, sec_id=sec_id)
+                                                   class_names=self.bbox_head.class_names, sec_id=sec_id, device_only=dev_only)
                 else:
-                    ret["seg"] = self.seg_head.predict(example, preds, self.test_cfg)
+                    ret["seg"] = self.seg_head.predict(example, preds, self.test_cfg, device_only=dev_only)
         if len(nxt):
             ret["next_context"] = nxt
         return ret
 
     def forward(self, example, return_loss=True, **kwargs):
+        """``device_only=True`` (inference): the sectors' detection lists stay on the device (``CenterHead.predict(device_only=True)``)
+        and the per-point outputs are flat tensors, so that from the first launch to the last nothing is read back or synchronised and
+        the sweep can be captured in one graph.  Returns 'det': the LAST sector's device list when the list is carried from sector to
+        sector (stateful NMS / panoptic), otherwise the list of per-sector device lists; 'seg' (and 'ins' under panoptic): lists of
+        per-sector flat (rows,) int64 tensors.  ``sweep_to_host`` turns that into what this method returns without the flag."""
         if isinstance(example, dict):
             return self.forward_one_sector(example, return_loss, **kwargs)
         stateful, panoptic = self._test_flag("stateful_nms"), self._test_flag("panoptic")
+        if kwargs.get("device_only", False) and not return_loss and not kwargs.get("raw_preds", False) and self.test_cfg is not None:
+            rets, prev = [], []
+            for i, ex in enumerate(example):
+                kw = dict(kwargs, prev_context=prev, sec_id=i)
+                if (stateful or panoptic) and i > 0:
+                    kw["prev_dets"] = rets[-1]["det"]
+                r = self.forward_one_sector(ex, False, **kw)
+                prev = r.pop("next_context", []) if i < len(example) - 1 else []
+                r.pop("next_context", None)
+                rets.append(r)
+            out = {"det": rets[-1]["det"] if (stateful or panoptic) else [r["det"] for r in rets]}
+            for k in ("seg", "ins"):
+                if k in rets[0]:
+                    out[k] = [r[k] for r in rets]
+            return out
         rets, prev = [], []
         for i, ex in enumerate(example):
             kw = dict(kwargs, prev_context=prev, sec_id=i)
@@ -306,6 +327,49 @@ class PolarStream(PointPillars):
             for det, meta in zip(out["det"], example[-1].get("metadata", [None] * len(out["det"]))):
                 det["metadata"] = meta
         return out
+
+    @staticmethod
+    def sweep_to_host(out, examples):
+        """The result of ``forward(examples, return_loss=False, device_only=True)`` -> exactly what ``forward(examples,
+        return_loss=False)`` returns: per-sample detections cut to their counts with 'metadata' (a carried list: the last sector's,
+        with 'instances' under panoptic; otherwise the sectors' lists concatenated, with 'cells'), and per-sample {token: tensor} dicts
+        for 'seg' / 'ins', the sectors' rows of a sample concatenated in sector order.  ONE readback, of the counts; the per-point
+        outputs are split by the host ``num_points``.  Index bookkeeping only: runs on whatever device the tensors live on."""
+        res = {}
+        det = out.get("det")
+        fields = ("box3d_lidar", "scores", "label_preds")
+        if isinstance(det, dict):        # carried from sector to sector: the last sector's list is the sweep's
+            counts = det["count"].tolist()
+            metas = examples[-1].get("metadata", [None] * len(counts))
+            res["det"] = []
+            for i, n in enumerate(counts):
+                d = {k: det[k][i, :n] for k in fields + (("instances",) if "instances" in det else ())}
+                d["metadata"] = metas[i]
+                res["det"].append(d)
+        elif det is not None:            # one list per sector: concatenated per sample (single_stage.py:118-135)
+            counts = torch.stack([d["count"] for d in det]).tolist()
+            metas = examples[0].get("metadata", [None] * len(counts[0]))
+            res["det"] = []
+            for i in range(len(counts[0])):
+                d = {k: torch.cat([s[k][i, :counts[j][i]] for j, s in enumerate(det)]) for k in fields + ("cells",)}
+                d["metadata"] = metas[i]
+                res["det"].append(d)
+        for key in ("seg", "ins"):
+            if key not in out:
+                continue
+            batch = len(examples[0]["num_points"])
+            merged = [{} for _ in range(batch)]
+            for ex, flat in zip(examples, out[key]):
+                num = ex["num_points"]
+                num = [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
+                start = 0
+                for i, n in enumerate(num):
+                    meta = ex["metadata"][i]
+                    token = meta["token"] if isinstance(meta, dict) and "token" in meta else i
+                    merged[i].setdefault(token, []).append(flat[start:start + n])
+                    start += n
+            res[key] = [{token: torch.cat(v) for token, v in m.items()} for m in merged]
+        return res
 
     def _test_flag(self, name) -> bool:
         cfg = self.test_cfg

@@ -216,21 +216,36 @@ class CenterHead(nn.Module):
         (center_head.py:466, 486-509).  Returns the reference's list (one dict per sample) of 'box3d_lidar' (n, 9|7), 'scores',
         'label_preds', 'metadata'.  test_cfg.panoptic (center_head.py:502-509, 552-573) adds 'instances' (int64, one id per box; the
         bookkeeping is ``panoptic_instance_ids``) and, like stateful NMS, returns the per-task lists unmerged (:438-439), the next
-        sector's prev_dets: without stateful NMS a later sector's list is then the previous list followed by the sector's own boxes."""
+        sector's prev_dets: without stateful NMS a later sector's list is then the previous list followed by the sector's own boxes.
+
+        ``device_only=True`` (one task): nothing is read back, the call can be captured in a hipGraph.  Returns ONE dict of fixed-capacity
+        buffers -- 'box3d_lidar' (B, cap, 9|7), 'scores' (B, cap), 'label_preds' (B, cap) int64, 'cells' (B, cap) int32, 'count' (B,)
+        int32, under panoptic 'instances' (B, cap) int64 (`pn_panoptic_box_ids`) --, rows at or past count[b] unspecified.  Under stateful
+        NMS or panoptic that dict is the next sector's ``prev_dets`` (None for sector 0) and cap = nms_post_max_size * (sec_id + 1): the
+        stateful kernel takes the previous buffers as they are, without stateful NMS `pn_det_list_append` builds the list.  Those two
+        flags need an explicit ``sec_id`` in this mode (sector streaming): a device_only call that names no sector is refused."""
         import ctypes as C
         lib = hip.load()
         get = (lambda k, d=None: test_cfg.get(k, d)) if hasattr(test_cfg, "get") else (lambda k, d=None: getattr(test_cfg, k, d))
         panoptic = bool(get("panoptic", False))         # center_head.py:467, 502-509, 552-573
         double_flip = bool(get("double_flip", False))   # center_head.py:412, 425-427
         stateful = bool(get("stateful_nms", False))     # center_head.py:466, 486-501, 507-509
-        if stateful and (double_flip or kwargs.get("device_only", False)):
-            raise NotImplementedError("predict: stateful NMS is not combined with double flip / device_only outputs")
-        if panoptic and (double_flip or kwargs.get("device_only", False)):
-            raise NotImplementedError("predict: test_cfg.panoptic is not combined with double flip / device_only outputs")
+        device_only = bool(kwargs.get("device_only", False))
+        if stateful and double_flip:
+            raise NotImplementedError("predict: stateful NMS is not combined with double flip")
+        if panoptic and double_flip:
+            raise NotImplementedError("predict: test_cfg.panoptic is not combined with double flip")
         per_class = bool(get("per_class_nms", False))   # batched_nms_rotated of the nuScenes configs (center_head.py:514-518)
-        if kwargs.get("device_only", False) and len(preds_dicts["det_preds"]) != 1:
+        if device_only and len(preds_dicts["det_preds"]) != 1:
             raise NotImplementedError("predict(device_only=True) supports a single task")
+        if device_only and (stateful or panoptic) and "sec_id" not in kwargs:
+            # a device list is carried from sector to sector and its capacity follows the sector: outside that protocol -- the one-shot
+            # device_only call of the frame engines, which names no sector -- stateful NMS / panoptic stay unbuilt
+            raise NotImplementedError("predict(device_only=True): test_cfg.stateful_nms / test_cfg.panoptic are built for sector streaming only: "
+                                      "the call must name its sector (sec_id; prev_dets = the dict the previous sector's call returned)")
         prev_dets = kwargs.get("prev_dets") if (stateful or panoptic) else None
+        if device_only and prev_dets is not None and not (isinstance(prev_dets, dict) and "count" in prev_dets):
+            raise TypeError("predict(device_only=True): prev_dets must be the dict the previous sector's device_only call returned")
         sec_id = int(kwargs.get("sec_id", 0))
         nms = get("nms")
         nget = (lambda k: nms[k]) if isinstance(nms, dict) else (lambda k: getattr(nms, k))
@@ -289,15 +304,21 @@ class CenterHead(nn.Module):
                 # frame first; the output may hold nms_post_max_size * (sec_id + 1) boxes
                 interval = float(get("interval")) if sec_id > 0 else 0.0
                 angle = (interval * sec_id if cyl else 2 * 3.141592653589793 / interval * sec_id) if sec_id > 0 else 0.0
-                prev = None if prev_dets is None else prev_dets[task_id]
-                pcap = 0 if prev is None else max([int(d["scores"].numel()) for d in prev] + [0])
                 pmax = post_max * (sec_id + 1)
                 f32 = dict(dtype=torch.float32, device=dev)
-                pb = torch.zeros((b, max(pcap, 1), nb), **f32)
-                ps = torch.zeros((b, max(pcap, 1)), **f32)
-                pl = torch.zeros((b, max(pcap, 1)), dtype=torch.int64, device=dev)
-                pc = torch.zeros((b,), dtype=torch.int32, device=dev)
-                if pcap:
+                if device_only:
+                    # the previous sector's fixed-capacity buffers go to the kernel as they are: rows past its count are ignored there
+                    prev = self._check_device_list(prev_dets, b, nb, dev)
+                    pcap = 0 if prev is None else int(prev["scores"].shape[1])
+                    pb, ps, pl, pc = (None,) * 4 if prev is None else (prev["box3d_lidar"], prev["scores"], prev["label_preds"], prev["count"])
+                else:
+                    prev = None if prev_dets is None else prev_dets[task_id]
+                    pcap = 0 if prev is None else max([int(d["scores"].numel()) for d in prev] + [0])
+                    pb = torch.zeros((b, max(pcap, 1), nb), **f32)
+                    ps = torch.zeros((b, max(pcap, 1)), **f32)
+                    pl = torch.zeros((b, max(pcap, 1)), dtype=torch.int64, device=dev)
+                    pc = torch.zeros((b,), dtype=torch.int32, device=dev)
+                if pcap and not device_only:
                     for i, d in enumerate(prev):
                         n = int(d["scores"].numel())
                         pb[i, :n].copy_(d["box3d_lidar"])
@@ -314,9 +335,15 @@ class CenterHead(nn.Module):
                          pd["height"].data_ptr(), pd["height"].stride(3), pd["dim"].data_ptr(), pd["dim"].stride(3), pd["rot"].data_ptr(),
                          pd["rot"].stride(3), hip.ptr(vel), 0 if vel is None else vel.stride(3), b, h, w, cyl, float(osf) * float(vs[0]),
                          float(osf) * float(vs[1]), float(pr[0]), float(pr[1]), int(bool(get("rectify", False))), float(get("score_threshold")),
-                         (C.c_float * 6)(*[float(v) for v in pcr]), iou_thr, int(per_class), pre_max, pmax, float(angle), pb.data_ptr(), ps.data_ptr(),
-                         pl.data_ptr(), pc.data_ptr(), pcap, out_boxes.data_ptr(), out_scores.data_ptr(), out_labels.data_ptr(), out_cells.data_ptr(),
+                         (C.c_float * 6)(*[float(v) for v in pcr]), iou_thr, int(per_class), pre_max, pmax, float(angle), hip.ptr(pb), hip.ptr(ps),
+                         hip.ptr(pl), hip.ptr(pc), pcap, out_boxes.data_ptr(), out_scores.data_ptr(), out_labels.data_ptr(), out_cells.data_ptr(),
                          out_count.data_ptr(), ws.data_ptr(), wsb, hip.stream())
+                if device_only:
+                    # the list stays on the device: fixed-capacity buffers + count, the next sector's prev_dets (hipGraph capturable)
+                    ret = dict(box3d_lidar=out_boxes, scores=out_scores, label_preds=out_labels, cells=out_cells, count=out_count)
+                    if panoptic:
+                        ret["instances"] = self._device_box_ids(ret, h * w, prev, sec_id, True)
+                    return ret
                 counts = out_count.cpu().tolist()
                 rets.append([dict(box3d_lidar=out_boxes[i, :n], scores=out_scores[i, :n], label_preds=out_labels[i, :n], cells=out_cells[i, :n])
                              for i, n in enumerate(counts)])
@@ -336,9 +363,28 @@ class CenterHead(nn.Module):
                 interval = float(get("interval"))
                 angle = interval * sec_id if cyl else 2 * 3.141592653589793 / interval * sec_id
                 hip.call("pn_rotate_boxes_f32", out_boxes.data_ptr(), out_count.data_ptr(), b, post_max, nb, float(angle), hip.stream())
-            if kwargs.get("device_only", False):
+            if device_only:
                 # fixed-size outputs + device counts: nothing leaves the stream (hipGraph capturable); one task only
-                return dict(box3d_lidar=out_boxes, scores=out_scores, label_preds=out_labels, cells=out_cells, count=out_count)
+                ret = dict(box3d_lidar=out_boxes, scores=out_scores, label_preds=out_labels, cells=out_cells, count=out_count)
+                if panoptic:
+                    # the sweep's list so far = the previous sectors' list followed by this sector's (rotated) boxes (center_head.py:562-571),
+                    # built on the device into nms_post_max_size * (sec_id + 1) rows; 'cells' stay each sector's own cell indices
+                    prev = None if sec_id == 0 else self._check_device_list(prev_dets, b, nb, dev)
+                    if sec_id > 0:
+                        pcap, cap = 0 if prev is None else int(prev["scores"].shape[1]), post_max * (sec_id + 1)
+                        if cap < pcap + post_max:
+                            raise ValueError(f"predict(device_only, panoptic): the previous list's capacity {pcap} exceeds nms_post_max_size * sec_id")
+                        lst = dict(box3d_lidar=torch.empty((b, cap, nb), dtype=torch.float32, device=dev), scores=torch.empty((b, cap), dtype=torch.float32, device=dev),
+                                   label_preds=torch.empty((b, cap), dtype=torch.int64, device=dev), cells=torch.empty((b, cap), dtype=torch.int32, device=dev),
+                                   count=torch.empty((b,), dtype=torch.int32, device=dev))
+                        pv = (lambda k: None) if prev is None else (lambda k: prev[k].data_ptr())
+                        hip.call("pn_det_list_append", pv("box3d_lidar"), pv("scores"), pv("label_preds"), pv("cells"), pv("count"), pcap,
+                                 out_boxes.data_ptr(), out_scores.data_ptr(), out_labels.data_ptr(), out_cells.data_ptr(), out_count.data_ptr(), post_max, b, nb,
+                                 lst["box3d_lidar"].data_ptr(), lst["scores"].data_ptr(), lst["label_preds"].data_ptr(), lst["cells"].data_ptr(),
+                                 lst["count"].data_ptr(), cap, hip.stream())
+                        ret = lst
+                    ret["instances"] = self._device_box_ids(ret, h * w, prev, sec_id, False)
+                return ret
             counts = out_count.cpu().tolist()  # the one host sync of the call: the API returns exact-size tensors
             rets.append([dict(box3d_lidar=out_boxes[i, :n], scores=out_scores[i, :n], label_preds=out_labels[i, :n], cells=out_cells[i, :n])
                          for i, n in enumerate(counts)])
@@ -366,6 +412,36 @@ class CenterHead(nn.Module):
             ret_list.append(dict(box3d_lidar=torch.cat([r[i]["box3d_lidar"] for r in rets]), scores=torch.cat([r[i]["scores"] for r in rets]),
                                  label_preds=torch.cat(labels), cells=torch.cat([r[i]["cells"] for r in rets]), metadata=metas[i]))
         return ret_list
+
+
+    @staticmethod
+    def _check_device_list(prev, b, nb, dev):
+        """the previous sector's device_only list (or None): (b, cap, nb) / (b, cap) / (b,) contiguous buffers on ``dev``, as predict returned them"""
+        if prev is None:
+            return None
+        cap = int(prev["scores"].shape[1])
+        want = dict(box3d_lidar=((b, cap, nb), torch.float32), scores=((b, cap), torch.float32), label_preds=((b, cap), torch.int64),
+                    cells=((b, cap), torch.int32), count=((b,), torch.int32))
+        if "instances" in prev:
+            want["instances"] = ((b, cap), torch.int64)
+        for k, (shape, dt) in want.items():
+            t = prev[k]
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"predict(device_only=True): prev_dets['{k}'] must be a contiguous {shape} {dt} tensor on {dev}")
+        return prev if cap else None
+
+    @staticmethod
+    def _device_box_ids(lst, cells, prev, sec_id, stateful):
+        """`pn_panoptic_box_ids` on a device list: the rules of ``panoptic_instance_ids`` with the counts read on the device -> (b, cap) int64"""
+        b, cap = lst["scores"].shape
+        ids = torch.empty((b, cap), dtype=torch.int64, device=lst["scores"].device)
+        if sec_id > 0 and prev is not None and "instances" not in prev:
+            raise ValueError("predict(device_only, panoptic): prev_dets carries no 'instances'")
+        pcap = 0 if (prev is None or sec_id == 0) else int(prev["scores"].shape[1])
+        hip.call("pn_panoptic_box_ids", lst["cells"].data_ptr(), lst["count"].data_ptr(), int(b), int(cap), int(cells),
+                 prev["instances"].data_ptr() if pcap else None, prev["count"].data_ptr() if pcap else None, pcap, int(sec_id), int(stateful),
+                 ids.data_ptr(), hip.stream())
+        return ids
 
 
 @BBOX_HEADS.register_module

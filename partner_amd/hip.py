@@ -165,6 +165,8 @@ SIGNATURES = {
     "pn_bilinear_upsample_add_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "pn_seg_point_labels": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
     "pn_panoptic_points_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _F, _P, _I, _P, _P, _P, _I, _P, _F, _P, _P, _P]),
+    "pn_panoptic_points_batched_f32": (_I, [_P, C.c_longlong, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _F, _F, _P, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P,
+                                            _P]),
     "pn_sparse_index_bytes": (_SZ, [_U64]),
     "pn_sparse_index_from_coords": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "pn_sparse_index_downsample": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
@@ -192,6 +194,8 @@ SIGNATURES = {
     "pn_swv_set_criterion_f32": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I,
                                       _F, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "pn_rotate_boxes_f32": (_I, [_P, _P, _I, _I, _I, C.c_double, _P]),
+    "pn_det_list_append": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "pn_panoptic_box_ids": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
     "pn_split_polar_sectors_workspace_bytes": (_SZ, [_I, _I, _I]),
     "pn_split_polar_sectors_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "pn_assemble_rows_f32": (_I, [C.POINTER(RowPiece), _I, _I, _I, _I, _P, _I, _I, _P]),

@@ -86,6 +86,12 @@ class SingleConvHead(nn.Module):
         assert seg.dim() == 4 and seg.stride(1) == 1, "seg_preds must be the channels-last view produced by forward"
         bsz, ncls, h, w = seg.shape
         cstride = seg.stride(3)                                  # padded channel count of the NHWC buffer
+        if kwargs.get("device_only", False):
+            # one launch for the sector, nothing read back: -> flat (rows,) int64, one label per point row in row order
+            gi, offs = self._flat_rows(example, seg.device)
+            labels = torch.empty((gi.shape[0],), dtype=torch.int64, device=seg.device)
+            self._launch_batched(seg, gi, offs, labels)
+            return labels
         out = []
         for i in range(bsz):
             gi = example["valid_grid_ind"][i]
@@ -102,8 +108,66 @@ class SingleConvHead(nn.Module):
             out.append({token: labels})
         return out
 
+    @staticmethod
+    def _flat_rows(example, dev):
+        """device_only inputs: the sector's grid indices as ONE (rows, 3) int64 tensor (``example['valid_grid_ind']``: that tensor, or the
+        per-sample list, concatenated on the device) and the samples' row offsets, device int32 (B + 1,): ``example['point_offsets']``
+        when present, otherwise built once from the host ``num_points`` and kept in the example (an upload: not capturable)"""
+        gi = example["valid_grid_ind"]
+        if not torch.is_tensor(gi):
+            hip.require_device(*gi)
+            gi = torch.cat([g.to(torch.int64) for g in gi], 0) if len(gi) > 1 else gi[0]
+        hip.require_device(gi)
+        gi = gi.to(torch.int64).contiguous()
+        assert gi.dim() == 2 and gi.shape[1] == 3, "valid_grid_ind must hold one [z, y, x] row per point"
+        offs = example.get("point_offsets")
+        if offs is None:
+            num = example["num_points"]
+            num = [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
+            assert sum(num) <= gi.shape[0], "num_points does not match valid_grid_ind"
+            acc = [0]
+            for v in num:
+                acc.append(acc[-1] + v)
+            offs = example["point_offsets"] = torch.tensor(acc, dtype=torch.int32, device=dev)
+        hip.require_device(offs)
+        assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous(), "point_offsets must be a contiguous int32 (B + 1,) tensor"
+        return gi, offs
+
+    def _launch_batched(self, seg, gi, offs, labels, points=None, x_col=0, angle=0.0, det=None, sem2box=None, score_thr=0.0, ins=None):
+        """`pn_panoptic_points_batched_f32` on the (possibly channel-padded) NHWC logits, read in place; det None: labels only"""
+        bsz, ncls, h, w = seg.shape
+        assert offs.shape[0] == bsz + 1, "point_offsets must have one entry per sample plus one"
+        assert seg.stride(2) == w * seg.stride(3) and (bsz == 1 or seg.stride(0) >= h * w * seg.stride(3))
+        if det is None:
+            hip.call("pn_panoptic_points_batched_f32", seg.data_ptr(), seg.stride(0) if bsz > 1 else 0, bsz, h, w, ncls, seg.stride(3), gi.data_ptr(),
+                     offs.data_ptr(), gi.shape[0], None, 0, 0, 1.0, 0.0, None, 0, 0, None, None, None, None, None, 0.0, labels.data_ptr(), None, hip.stream())
+            return
+        boxes = det["box3d_lidar"]
+        cap = int(boxes.shape[1])
+        point_stride = points.stride(0) if points.shape[0] > 1 else points.shape[1]
+        hip.call("pn_panoptic_points_batched_f32", seg.data_ptr(), seg.stride(0) if bsz > 1 else 0, bsz, h, w, ncls, seg.stride(3), gi.data_ptr(),
+                 offs.data_ptr(), gi.shape[0], points.data_ptr(), point_stride, x_col, math.cos(angle), math.sin(angle), boxes.data_ptr(), boxes.stride(1), cap,
+                 det["scores"].data_ptr(), det["label_preds"].data_ptr(), det["instances"].data_ptr(), det["count"].data_ptr(), sem2box.data_ptr(),
+                 float(score_thr), labels.data_ptr(), ins.data_ptr(), hip.stream())
+
+    def _sem2box(self, class_names, semantic2box, ncls, dev):
+        """DEVICE int32 table semantic label -> box label (-1: stuff), cached on the head per (class names, device): uploaded once"""
+        names = [n for sub in class_names for n in ([sub] if isinstance(sub, str) else sub)]
+        things = SEMANTIC2BOX if semantic2box is None else list(semantic2box)
+        key = (tuple(names), tuple(things), int(ncls), str(dev))
+        cache = self.__dict__.setdefault("_sem2box_cache", {})
+        if key not in cache:
+            table = [-1] * (ncls + 1)
+            for k, name in enumerate(things[:ncls]):
+                if name not in names:
+                    raise ValueError(f"predict_panoptic: semantic label {k + 1} maps to the box class '{name}', which is not among the head's class_names {names}")
+                table[k + 1] = names.index(name)
+            cache[key] = torch.tensor(table, dtype=torch.int32, device=dev)
+        return cache[key]
+
     @torch.no_grad()
-    def predict_panoptic(self, example, preds_dicts, test_cfg, ret_dict, *, voxel_shape, class_names, sec_id, semantic2box=None, score_thr=0.3):
+    def predict_panoptic(self, example, preds_dicts, test_cfg, ret_dict, *, voxel_shape, class_names, sec_id, semantic2box=None, score_thr=0.3,
+                         device_only=False):
         """panoptic fusion (seg_head.py:99-168): the per-point semantic labels of ``predict`` plus, for every point, the instance id of
         the nearest box centre of its class, one launch per sample (`pn_panoptic_points_f32`).  Fills ``ret_dict['seg']`` and
         ``ret_dict['ins']`` (lists of {token: (n_i,) int64}; the reference wraps them in iterators) and returns ``ret_dict``.
@@ -114,20 +178,18 @@ class SingleConvHead(nn.Module):
         the flattened ``class_names`` is the box label (ValueError when the name is missing).  Eligible boxes have that label and
         score > ``score_thr``; the point's Cartesian (x, y) -- columns 3:5 of a polar point row (``voxel_shape='cylinder'``), 0:2
         otherwise -- is rotated by the sector angle (``interval * sec_id``; cuboid: ``2 pi / interval * sec_id``) first.  Stuff points
-        and things without an eligible box get 0 -- which is also the id of the sweep's first box (the reference's ids start at 0)."""
+        and things without an eligible box get 0 -- which is also the id of the sweep's first box (the reference's ids start at 0).
+
+        ``device_only=True``: ``ret_dict['det']`` is the device list of ``CenterHead.predict(device_only=True)`` (with 'instances'), all
+        samples run in ONE launch (`pn_panoptic_points_batched_f32`: box counts and point offsets are read on the device) and
+        ``ret_dict['seg']`` / ``ret_dict['ins']`` are flat (rows,) int64 tensors, one entry per point row of the sector in row order.
+        Nothing is read back and, after a first call has cached the class table, nothing is uploaded: the call can be captured."""
         seg = preds_dicts["seg_preds"]
         hip.require_device(seg)
         assert seg.dim() == 4 and seg.stride(1) == 1, "seg_preds must be the channels-last view produced by forward"
         bsz, ncls, h, w = seg.shape
         dev = seg.device
-        names = [n for sub in class_names for n in ([sub] if isinstance(sub, str) else sub)]
-        things = SEMANTIC2BOX if semantic2box is None else list(semantic2box)
-        table = [-1] * (ncls + 1)
-        for k, name in enumerate(things[:ncls]):
-            if name not in names:
-                raise ValueError(f"predict_panoptic: semantic label {k + 1} maps to the box class '{name}', which is not among the head's class_names {names}")
-            table[k + 1] = names.index(name)
-        sem2box = torch.tensor(table, dtype=torch.int32, device=dev)
+        sem2box = self._sem2box(class_names, semantic2box, ncls, dev)
         sec_id = int(sec_id)
         angle = 0.0
         if sec_id > 0:
@@ -139,6 +201,24 @@ class SingleConvHead(nn.Module):
         assert points.dim() == 2 and points.dtype == torch.float32 and points.shape[1] >= x_col + 2
         if points.numel() and points.stride(1) != 1:
             points = points.contiguous()
+        if device_only:
+            det = ret_dict["det"]
+            if not (isinstance(det, dict) and "instances" in det and "count" in det):
+                raise TypeError("predict_panoptic(device_only=True): ret_dict['det'] must be the device list of CenterHead.predict(device_only=True) under test_cfg.panoptic")
+            hip.require_device(*det.values())
+            gi, offs = self._flat_rows(example, dev)
+            assert gi.shape[0] <= points.shape[0], "valid_grid_ind has more rows than the point list"
+            boxes = det["box3d_lidar"]
+            cap = int(boxes.shape[1])
+            assert boxes.dim() == 3 and boxes.shape[0] == bsz and boxes.dtype == torch.float32 and boxes.stride(2) == 1 and boxes.stride(0) == cap * boxes.stride(1)
+            for k, dt in (("scores", torch.float32), ("label_preds", torch.int64), ("instances", torch.int64)):
+                assert tuple(det[k].shape) == (bsz, cap) and det[k].dtype == dt and det[k].is_contiguous(), f"the device list's '{k}' must be a contiguous (B, cap) tensor"
+            assert tuple(det["count"].shape) == (bsz,) and det["count"].dtype == torch.int32
+            labels = torch.empty((gi.shape[0],), dtype=torch.int64, device=dev)
+            ins = torch.empty((gi.shape[0],), dtype=torch.int64, device=dev)
+            self._launch_batched(seg, gi, offs, labels, points, x_col, angle, det, sem2box, score_thr, ins)
+            ret_dict["seg"], ret_dict["ins"] = labels, ins
+            return ret_dict
         point_stride = points.stride(0) if points.shape[0] > 1 else points.shape[1]      # (the stride of a 0- or 1-row tensor is arbitrary)
         num = example["num_points"]
         num = [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
