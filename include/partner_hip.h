@@ -1390,6 +1390,19 @@ int pn_l2_normalize_bwd_f32(const float *y, const float *dy, const float *inv_no
  * (voxelization.py:447); bilinear, zero padding, align_corners = False (torch.nn.functional.grid_sample defaults). */
 int pn_polar_warp_f32(const float *in, const float *rot2x2, int batch, int nsectors, int h, int w, int c, float range_lo,
                       float range_hi, float azimuth_lo, float azimuth_hi, float *out, pn_stream_t stream);
+/* The same warp for the rows the streaming pass reads, ALL layers in one launch (RPNBDCP._pad_streaming takes `pad` rows at every
+ * sector border and nothing else of the previous sweep).  Job j (of njobs <= 32): `in` = layer j's stacked sector-major
+ * (nsectors * batch, h / nsectors, w, c) map, `out` = (batch, (nsectors + 1) * pad, w, c): with hs = h / nsectors, strip k < nsectors
+ * holds rows [k * hs, k * hs + pad) of what pn_polar_warp_f32 writes for that map, strip nsectors rows [h - pad, h) -- bit for bit,
+ * both kernels run the same per-cell code.  rot2x2, batch, nsectors, pad and the bounds are shared by the jobs.  Refused: c % 4 != 0,
+ * pad > hs, h % nsectors != 0, null or misaligned (16 bytes) maps, an output overlapping any input or another output. */
+typedef struct {
+  const float *in;
+  float *out;
+  int32_t h, w, c;
+} pn_warp_strip_job;
+int pn_polar_warp_strips_f32(const pn_warp_strip_job *jobs, int njobs, const float *rot2x2, int batch, int nsectors, int pad,
+                             float range_lo, float range_hi, float azimuth_lo, float azimuth_hi, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * next-4  global augmentation of one training sample, in place on the device: points (n, point_stride >= 3) [x, y, z, ...]

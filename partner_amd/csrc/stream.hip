@@ -2,6 +2,8 @@
 //   pn_split_polar_sectors_f32   Voxelization.voxelize_streaming_polar, det3d/datasets/pipelines/voxelization.py:305-393:
 //                                stable partition of the polar points by (sector, sample), azimuth shifted into the first sector's
 //                                range, x / y recomputed, grid indices against the sector grid
+//   pn_polar_warp_f32 / _strips  the ego-motion warp of the previous sweep's per-layer maps (PolarStreamBDCP): whole maps, or in one launch
+//                                for all layers only the border rows the streaming pass reads
 //   pn_assemble_rows_f32         the row concatenations of the context-padding convolutions ConvContext / ConvBDCP,
 //                                det3d/models/necks/rpn_context.py:10-44, 98-158 (torch.cat / F.pad along the azimuth axis):
 //                                every output sample = up to three row pieces taken from other maps (or zeros)
@@ -155,43 +157,92 @@ struct WarpArgs {
   float lo_r, hi_r, lo_a, hi_a;
   int nsec, hs;   // input stacked sector-major: sample (sector * B + b), hs = H / nsec rows each
 };
+// the bounds of the polar map and what get_center derives from them: the same few fp32 operations wherever a cell is resampled
+struct WarpFrame {
+  float lo_r, lo_a, span_r, span_a, cen_r, cen_a, half_r, half_a;
+  __device__ __forceinline__ WarpFrame(float lo_r_, float hi_r_, float lo_a_, float hi_a_)
+      : lo_r(lo_r_), lo_a(lo_a_), span_r(hi_r_ - lo_r_), span_a(hi_a_ - lo_a_), cen_r((hi_r_ + lo_r_) * 0.5f), cen_a((hi_a_ + lo_a_) * 0.5f),
+        half_r(span_r * 0.5f), half_a(span_a * 0.5f) {}
+};
+// ONE output cell (sample b, azimuth row m, range column n, channels 4q .. 4q + 3) of the warped whole-sweep (H, W, C) map, read from the
+// sector-major stack `in`: the arithmetic of both the whole-map kernel and the strip kernel, so that a strip row is the whole map's row
+__device__ __forceinline__ f32x4 warp_cell(const float* in, const float* rot, const WarpFrame& f, int B, int H, int W, int C, int hs, int b, int m,
+                                           int n, int q) {
+  const float az = f.span_a / (float)H * (float)m + f.lo_a;
+  const float rr = f.span_r / (float)W * (float)n + f.lo_r;
+  const float x = rr * cosf(az), y = rr * sinf(az);
+  const float* t = rot + (size_t)b * 4;
+  const float xs = t[0] * x + t[1] * y, ys = t[2] * x + t[3] * y;
+  const float rho = sqrtf(xs * xs + ys * ys), phi = atan2f(ys, xs);
+  const float gx = (rho - f.cen_r) / f.half_r, gy = (phi - f.cen_a) / f.half_a;
+  const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+  const float fx = floorf(ix), fy = floorf(iy);
+  const int x0 = (int)fx, y0 = (int)fy;
+  const float wx1 = ix - fx, wy1 = iy - fy, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  const float* base = in + q * 4;
+  auto tap = [&](int yy, int xx, float wgt) {
+    if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+      const int sec = yy / hs, ys_ = yy - sec * hs;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(base + ((((size_t)sec * B + b) * hs + ys_) * W + xx) * C);
+      acc += v * wgt;
+    }
+  };
+  tap(y0, x0, wy0 * wx0);
+  tap(y0, x0 + 1, wy0 * wx1);
+  tap(y0 + 1, x0, wy1 * wx0);
+  tap(y0 + 1, x0 + 1, wy1 * wx1);
+  return acc;
+}
+
 __global__ void polar_warp_kernel(WarpArgs a) {
   const int c4 = a.C >> 2;
   const long long total = (long long)a.B * a.H * a.W * c4;
-  const float span_r = a.hi_r - a.lo_r, span_a = a.hi_a - a.lo_a;
-  const float cen_r = (a.hi_r + a.lo_r) * 0.5f, cen_a = (a.hi_a + a.lo_a) * 0.5f, half_r = span_r * 0.5f, half_a = span_a * 0.5f;
+  const WarpFrame f(a.lo_r, a.hi_r, a.lo_a, a.hi_a);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int q = (int)(i % c4);
     long long r = i / c4;
     const int n = (int)(r % a.W); r /= a.W;
     const int m = (int)(r % a.H);
     const int b = (int)(r / a.H);
-    const float az = span_a / (float)a.H * (float)m + a.lo_a;
-    const float rr = span_r / (float)a.W * (float)n + a.lo_r;
-    const float x = rr * cosf(az), y = rr * sinf(az);
-    const float* t = a.rot + (size_t)b * 4;
-    const float xs = t[0] * x + t[1] * y, ys = t[2] * x + t[3] * y;
-    const float rho = sqrtf(xs * xs + ys * ys), phi = atan2f(ys, xs);
-    const float gx = (rho - cen_r) / half_r, gy = (phi - cen_a) / half_a;
-    const float ix = ((gx + 1.f) * (float)a.W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)a.H - 1.f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const float wx1 = ix - fx, wy1 = iy - fy, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const float* base = a.in + q * 4;
-    auto tap = [&](int yy, int xx, float wgt) {
-      if ((unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W) {
-        const int sec = yy / a.hs, ys_ = yy - sec * a.hs;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(base + ((((size_t)sec * a.B + b) * a.hs + ys_) * a.W + xx) * a.C);
-        acc += v * wgt;
-      }
-    };
-    tap(y0, x0, wy0 * wx0);
-    tap(y0, x0 + 1, wy0 * wx1);
-    tap(y0 + 1, x0, wy1 * wx0);
-    tap(y0 + 1, x0 + 1, wy1 * wx1);
-    *reinterpret_cast<f32x4*>(a.out + i * 4) = acc;
+    *reinterpret_cast<f32x4*>(a.out + i * 4) = warp_cell(a.in, a.rot, f, a.B, a.H, a.W, a.C, a.hs, b, m, n, q);
   }
+}
+
+// ---- the same warp for the rows the streaming pass reads (RPNBDCP._pad_streaming: `pad` rows at every sector border), ALL layers in one
+// launch.  Per layer (job) the output holds nsec + 1 strips of `pad` rows: strip k < nsec = rows [k * hs, k * hs + pad) of the warped
+// whole-sweep map, strip nsec = rows [H - pad, H).  One thread per (cell, 4 channels); a block belongs to ONE job, found in the prefix
+// table of block counts (uniform across the block).
+constexpr int kMaxStripJobs = 32, kStripT = 256;
+struct StripJob {
+  const float* in; float* out;
+  int H, W, C, hs;
+};
+struct StripArgs {
+  StripJob job[kMaxStripJobs];
+  unsigned first_block[kMaxStripJobs + 1];   // job j owns blocks [first_block[j], first_block[j + 1])
+  int njobs;
+  const float* rot;
+  int B, nsec, pad;
+  float lo_r, hi_r, lo_a, hi_a;
+};
+__global__ __launch_bounds__(kStripT) void polar_warp_strips_kernel(StripArgs a) {
+  int j = 0;
+  while (j + 1 < a.njobs && blockIdx.x >= a.first_block[j + 1]) ++j;
+  const StripJob& jb = a.job[j];
+  const int c4 = jb.C >> 2, rows = (a.nsec + 1) * a.pad;
+  const long long total = (long long)a.B * rows * jb.W * c4;
+  const long long i = (long long)(blockIdx.x - a.first_block[j]) * kStripT + threadIdx.x;
+  if (i >= total) return;
+  const int q = (int)(i % c4);
+  long long r = i / c4;
+  const int n = (int)(r % jb.W); r /= jb.W;
+  const int sr = (int)(r % rows);
+  const int b = (int)(r / rows);
+  const int k = sr / a.pad, within = sr - k * a.pad;
+  const int m = k < a.nsec ? k * jb.hs + within : jb.H - a.pad + within;
+  const WarpFrame f(a.lo_r, a.hi_r, a.lo_a, a.hi_a);
+  *reinterpret_cast<f32x4*>(jb.out + i * 4) = warp_cell(jb.in, a.rot, f, a.B, jb.H, jb.W, jb.C, jb.hs, b, m, n, q);
 }
 
 }  // namespace
@@ -260,6 +311,44 @@ int pn_polar_warp_f32(const float* in, const float* rot2x2, int batch, int nsect
   const long long total = (long long)batch * h * w * (c / 4);
   hipLaunchKernelGGL(polar_warp_kernel, dim3((unsigned)std::min<long long>(65535, (total + 255) / 256)), dim3(256), 0, pn::S(stream), a);
   return pn::check_launch("polar_warp_kernel");
+}
+
+int pn_polar_warp_strips_f32(const pn_warp_strip_job* jobs, int njobs, const float* rot2x2, int batch, int nsectors, int pad, float range_lo,
+                             float range_hi, float azimuth_lo, float azimuth_hi, pn_stream_t stream) {
+  PN_REQUIRE(jobs && rot2x2 && njobs >= 1 && njobs <= kMaxStripJobs, "polar_warp_strips: null pointer or more than 32 jobs");
+  PN_REQUIRE(batch >= 1 && nsectors >= 1 && pad >= 1, "polar_warp_strips: bad sizes");
+  PN_REQUIRE(range_hi > range_lo && azimuth_hi > azimuth_lo, "polar_warp_strips: empty range");
+  StripArgs a;
+  a.njobs = njobs; a.rot = rot2x2; a.B = batch; a.nsec = nsectors; a.pad = pad;
+  a.lo_r = range_lo; a.hi_r = range_hi; a.lo_a = azimuth_lo; a.hi_a = azimuth_hi;
+  const long long rows = (long long)(nsectors + 1) * pad;
+  long long blocks = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const pn_warp_strip_job& s = jobs[j];
+    PN_REQUIRE(s.in && s.out, "polar_warp_strips: null map");
+    PN_REQUIRE((((uintptr_t)s.in | (uintptr_t)s.out) & 15) == 0, "polar_warp_strips: maps must be 16-byte aligned");
+    PN_REQUIRE(s.h >= 1 && s.w >= 1 && s.c >= 4 && s.c % 4 == 0, "polar_warp_strips: bad map shape (channels a multiple of 4)");
+    PN_REQUIRE(s.h % nsectors == 0, "polar_warp_strips: the azimuth rows must divide into the sectors");
+    PN_REQUIRE(pad <= s.h / nsectors, "polar_warp_strips: pad exceeds the rows of a sector");
+    a.job[j] = StripJob{s.in, s.out, s.h, s.w, s.c, s.h / nsectors};
+    a.first_block[j] = (unsigned)blocks;
+    blocks += ((long long)batch * rows * s.w * (s.c / 4) + kStripT - 1) / kStripT;
+    PN_REQUIRE(blocks < (1ll << 31), "polar_warp_strips: too many cells for one launch");
+  }
+  a.first_block[njobs] = (unsigned)blocks;
+  // no output may overlap an input or another output: the launch reads and writes all jobs at once
+  for (int i = 0; i < njobs; ++i) {
+    const uintptr_t o0 = (uintptr_t)jobs[i].out, o1 = o0 + sizeof(float) * batch * rows * jobs[i].w * jobs[i].c;
+    for (int j = 0; j < njobs; ++j) {
+      const uintptr_t i0 = (uintptr_t)jobs[j].in, i1 = i0 + sizeof(float) * batch * jobs[j].h * jobs[j].w * jobs[j].c;
+      PN_REQUIRE(o1 <= i0 || i1 <= o0, "polar_warp_strips: an output overlaps an input");
+      if (j == i) continue;
+      const uintptr_t p0 = (uintptr_t)jobs[j].out, p1 = p0 + sizeof(float) * batch * rows * jobs[j].w * jobs[j].c;
+      PN_REQUIRE(o1 <= p0 || p1 <= o0, "polar_warp_strips: two outputs overlap");
+    }
+  }
+  hipLaunchKernelGGL(polar_warp_strips_kernel, dim3((unsigned)blocks), dim3(kStripT), 0, pn::S(stream), a);
+  return pn::check_launch("polar_warp_strips_kernel");
 }
 
 }  // extern "C"

@@ -462,48 +462,177 @@ class PolarStreamBDCP(PolarStream):
             out.append(warped)
         return out
 
-    def forward_one_sweep(self, example, mode="feature_only", return_loss=False, **kwargs):
+    def warp_prev_strips(self, cur_sweep, transform, bs):
+        """``warp_prev_sweep`` for the rows the streaming pass reads and nothing else: ONE `pn_polar_warp_strips_f32` launch for all layers
+        -> per layer a ``PrevStrips`` pack (bs, (nsectors + 1) * pad, w, c), bit for bit the rows of the whole warped map.  ``transform``
+        may live on the device already (nothing is uploaded then)."""
+        from .necks_context import PrevStrips
+        pr = self._get("pc_range")
+        nsec = self.nsectors
+        dev = cur_sweep[0].device
+        rot = torch.as_tensor(transform)[:bs].to(dev).float().contiguous()
+        pad = max(int(cc.padding) for blk in self.neck.blocks for cc in blk._modules.values())
+        rows = (nsec + 1) * pad
+        sizes = [bs * rows * x.shape[2] * x.shape[3] for x in cur_sweep]
+        flat = torch.empty((sum(sizes),), dtype=torch.float32, device=dev)
+        jobs = (hip.WarpStripJob * len(cur_sweep))()
+        out, at = [], 0
+        for k, x in enumerate(cur_sweep):
+            n, hs, w, c = x.shape
+            assert n == nsec * bs and x.is_contiguous() and x.dtype == torch.float32
+            strips = flat[at:at + sizes[k]].view(bs, rows, w, c)
+            at += sizes[k]
+            jobs[k].in_, jobs[k].out, jobs[k].h, jobs[k].w, jobs[k].c = x.data_ptr(), strips.data_ptr(), nsec * hs, w, c
+            out.append(PrevStrips(strips, nsec, pad, hs))
+        hip.call("pn_polar_warp_strips_f32", jobs, len(cur_sweep), rot.data_ptr(), bs, nsec, pad, float(pr[0]), float(pr[3]), float(pr[1]), float(pr[4]),
+                 hip.stream())
+        return out
+
+    def _stream_sectors(self, canvas, prev_sweep, bs, mode):
+        """the current sweep through the neck, sector by sector (polarstream.py:386-402) -> the stacked neck output"""
+        nsec = self.nsectors
+        if nsec == 1:
+            return self.neck.forward_nhwc(canvas, prev_sweep=prev_sweep, nsectors=1, mode=mode)[0]
+        outs, ctx = [], []
+        for j in range(nsec):
+            y, ctx = self.neck.forward_nhwc(canvas[j * bs:(j + 1) * bs].contiguous(), prev_sweep=prev_sweep, prev_context=ctx, sec_id=j, nsectors=nsec,
+                                            mode=mode)
+            outs.append(y)
+        return torch.cat(outs, 0)
+
+    def _refuse_unbuilt(self, return_loss):
         eval_only(self, "PolarStreamBDCP")
         if return_loss:
             raise NotImplementedError("PolarStreamBDCP: training (the two-sweep loss path) is not built")
         if self._test_flag("panoptic"):
             raise NotImplementedError("PolarStreamBDCP: test_cfg.panoptic (polarstream.py:423-460) is not built; PolarStream has it")
+
+    def forward_one_sweep(self, example, mode="feature_only", return_loss=False, **kwargs):
+        self._refuse_unbuilt(return_loss)
         canvas, batch = self._canvas(example)
         nsec = self.nsectors
         bs = batch // nsec
         if mode == "feature_only":
             _, cur = self.neck.forward_nhwc(canvas, nsectors=nsec, mode="feature_only")
             return self.warp_prev_sweep(cur, torch.as_tensor(example["transform_matrix"])[:bs], bs)
-        prev_sweep = kwargs["prev_sweep"]
-        if nsec == 1:
-            x2, _ = self.neck.forward_nhwc(canvas, prev_sweep=prev_sweep, nsectors=1, mode=mode)
-        else:
-            outs, ctx = [], []
-            for j in range(nsec):
-                y, ctx = self.neck.forward_nhwc(canvas[j * bs:(j + 1) * bs].contiguous(), prev_sweep=prev_sweep, prev_context=ctx, sec_id=j, nsectors=nsec,
-                                                mode=mode)
-                outs.append(y)
-            x2 = torch.cat(outs, 0)
-        preds = self.bbox_head(ops.as_nchw(x2))
+        x2 = self._stream_sectors(canvas, kwargs["prev_sweep"], bs, mode)
+        preds = self._heads(canvas, x2)             # polarstream.py:404-408: the seg head (when there is one) on the stacked canvases + neck output
+        cut = lambda i: {"det_preds": [{k: v[i * bs:(i + 1) * bs] for k, v in t.items()} for t in preds["det_preds"]],  # noqa: E731
+                         **({"seg_preds": preds["seg_preds"][i * bs:(i + 1) * bs]} if "seg_preds" in preds else {})}
         if kwargs.get("raw_preds", False) or self.test_cfg is None:
-            return [dict(det_preds=[{k: v[i * bs:(i + 1) * bs] for k, v in t.items()} for t in preds["det_preds"]]) for i in range(nsec)]
+            return [cut(i) for i in range(nsec)]
         stateful = bool(self._get("stateful_nms", False))
         rets, prev_dets = [], None
         metas = example.get("metadata", [None] * batch)
         for i in range(nsec):
-            pr = {"det_preds": [{k: v[i * bs:(i + 1) * bs] for k, v in t.items()} for t in preds["det_preds"]]}
+            pr = cut(i)
             ex = dict(metadata=metas[i * bs:(i + 1) * bs])
             if "pc_range" in example:
                 ex["pc_range"] = example["pc_range"][i * bs:(i + 1) * bs]
             det = self.bbox_head.predict(ex, pr, self.test_cfg, sec_id=i, prev_dets=prev_dets)
             rets.append({"det": det})
             prev_dets = det if stateful and i < nsec - 1 else None
+            if self.seg_head is not None:           # polarstream.py:449-463
+                for k in ("num_points", "valid_grid_ind"):
+                    ex[k] = example[k][i * bs:(i + 1) * bs]
+                rets[i]["seg"] = self.seg_head.predict(ex, pr, self.test_cfg)
         return rets
 
+    def _point_rows(self, example, dev):
+        """the stacked sweep's per-point grid indices as ONE (rows, 3) int64 device tensor and the (nsectors * bs + 1,) int32 row offsets
+        of its samples: ``example['point_offsets']`` when present, otherwise built once from the host ``num_points`` and kept in the
+        example (an upload: not capturable), as ``SingleConvHead._flat_rows`` does for a sector"""
+        gi = example["valid_grid_ind"]
+        if not torch.is_tensor(gi):
+            hip.require_device(*gi)
+            gi = torch.cat([g.to(torch.int64) for g in gi], 0) if len(gi) > 1 else gi[0]
+        hip.require_device(gi)
+        gi = gi.to(torch.int64).contiguous()
+        offs = example.get("point_offsets")
+        if offs is None:
+            acc = [0]
+            for v in self._host_counts(example):
+                acc.append(acc[-1] + v)
+            offs = example["point_offsets"] = torch.tensor(acc, dtype=torch.int32, device=dev)
+        hip.require_device(offs)
+        assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous() and offs.shape[0] == len(example["num_points"]) + 1, \
+            "point_offsets must be a contiguous int32 (nsectors * bs + 1,) tensor"
+        return gi, offs
+
+    @staticmethod
+    def _host_counts(example):
+        num = example["num_points"]
+        return [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
+
+    def prev_sweep_strips(self, example):
+        """the previous sweep's pass of the device path: canvas, the neck up to its last layer's input, one strip-warp launch
+        -> per layer a ``PrevStrips`` pack (what ``forward_one_sweep(example, 'feature_only')`` returns as whole maps)"""
+        canvas, batch = self._canvas(example)
+        _, cur = self.neck.forward_nhwc(canvas, nsectors=self.nsectors, mode="feature_only", inputs_only=True)
+        return self.warp_prev_strips(cur, example["transform_matrix"], batch // self.nsectors)
+
+    def _forward_device(self, example, **kwargs):
+        """``forward(..., device_only=True)``: the two-sweep step with nothing read back or synchronised, so that it can be captured in one
+        graph.  The previous sweep runs the canvas and the neck up to its last layer's input (no last convolution, no deblocks: nobody
+        reads them), and ONE launch warps the border rows the current sweep's streaming pass reads; with one sector the padding is
+        circular and the previous sweep is skipped altogether.  The current sweep is the host path's, with the heads' ``device_only`` calls
+        per sector."""
+        self._refuse_unbuilt(False)
+        prev_ex, ex = example
+        nsec = self.nsectors
+        prev_sweep = self.prev_sweep_strips(prev_ex) if nsec > 1 else []
+        canvas, batch = self._canvas(ex)
+        bs = batch // nsec
+        preds = self._heads(canvas, self._stream_sectors(canvas, prev_sweep, bs, "eval"))
+        stateful = bool(self._get("stateful_nms", False))
+        metas = ex.get("metadata", [None] * batch)
+        dets, segs, prev_dets = [], [], None
+        if self.seg_head is not None:
+            gi, offs = self._point_rows(ex, canvas.device)
+            first = [0]
+            for v in self._host_counts(ex):
+                first.append(first[-1] + v)
+        for i in range(nsec):
+            sec = dict(metadata=metas[i * bs:(i + 1) * bs])
+            if "pc_range" in ex:
+                sec["pc_range"] = ex["pc_range"][i * bs:(i + 1) * bs]
+            pr = {"det_preds": [{k: v[i * bs:(i + 1) * bs] for k, v in t.items()} for t in preds["det_preds"]]}
+            prev_dets = self.bbox_head.predict(sec, pr, self.test_cfg, sec_id=i, prev_dets=prev_dets if stateful else None, device_only=True)
+            dets.append(prev_dets)
+            if self.seg_head is not None:
+                # the sector's samples are rows [offs[i * bs], offs[(i + 1) * bs]) of the sweep's flat list: the kernel takes absolute offsets, so
+                # the head gets the whole list with the sector's offsets and writes the sector's rows, which the host counts cut out
+                rows = dict(valid_grid_ind=gi, point_offsets=offs[i * bs:(i + 1) * bs + 1])
+                labels = self.seg_head.predict(rows, {"seg_preds": preds["seg_preds"][i * bs:(i + 1) * bs]}, self.test_cfg, device_only=True)
+                segs.append(labels[first[i * bs]:first[(i + 1) * bs]])
+        out = {"det": dets[-1] if stateful else dets}
+        if self.seg_head is not None:
+            out["seg"] = segs
+        return out
+
+    def sweep_to_host(self, out, cur_example):
+        """The result of ``forward([prev, cur], return_loss=False, device_only=True)`` -> exactly what ``forward([prev, cur],
+        return_loss=False)`` returns, with ONE readback (the counts): the stacked example is cut into its sectors' host fields and handed
+        to ``PolarStream.sweep_to_host``; a carried list takes the first sector's metadata, as ``forward`` gives it."""
+        nsec = self.nsectors
+        num = self._host_counts(cur_example)
+        bs = len(num) // nsec
+        metas = cur_example.get("metadata", [None] * len(num))
+        sectors = [dict(num_points=num[i * bs:(i + 1) * bs], metadata=metas[i * bs:(i + 1) * bs]) for i in range(nsec)]
+        res = PolarStream.sweep_to_host(out, sectors)
+        if isinstance(out.get("det"), dict):
+            for det, meta in zip(res["det"], metas[:bs]):
+                det["metadata"] = meta
+        return res
+
     def forward(self, example, return_loss=True, **kwargs):
-        """example: [previous sweep, current sweep] (polarstream.py:266-290)"""
+        """example: [previous sweep, current sweep] (polarstream.py:266-290).  ``device_only=True`` (inference): see ``_forward_device``;
+        returns 'det': the last sector's device list under stateful NMS, otherwise the list of per-sector device lists, and with a seg head
+        'seg': the sectors' flat (rows,) int64 label tensors.  ``sweep_to_host`` turns that into what this method returns without the flag."""
         if isinstance(example, dict) or len(example) != 2:
             raise ValueError("PolarStreamBDCP.forward takes a list of two sweeps [previous, current]")
+        if kwargs.get("device_only", False) and not return_loss and not kwargs.get("raw_preds", False) and self.test_cfg is not None:
+            return self._forward_device(example, **kwargs)
         prev_sweep = self.forward_one_sweep(example[0], "feature_only", False, **kwargs)
         rets = self.forward_one_sweep(example[1], "train" if return_loss else "eval", return_loss, prev_sweep=prev_sweep, **kwargs)
         ex = example[1]

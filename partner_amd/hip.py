@@ -36,6 +36,12 @@ class RowPiece(C.Structure):
     _fields_ = [("src", C.c_void_p), ("pixel_stride", C.c_int32), ("rows", C.c_int32)]
 
 
+class WarpStripJob(C.Structure):
+    """mirror of ``pn_warp_strip_job``"""
+
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32)]
+
+
 class HeadStatJob(C.Structure):
     """mirror of ``pn_head_stat_job``"""
 
@@ -275,6 +281,7 @@ SIGNATURES = {
     "pn_pillar_conv_wgrad_workspace_bytes": (_SZ, [_I, _I, _I]),
     "pn_pillar_conv3x3_wgrad_f32": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _SZ, _P]),
     "pn_polar_warp_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P]),
+    "pn_polar_warp_strips_f32": (_I, [C.POINTER(WarpStripJob), _I, _P, _I, _I, _I, _F, _F, _F, _F, _P]),
     "pn_contract_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "pn_softmax_f32": (_I, [_P, _P, C.c_longlong, _I, _I, _P]),
     "pn_softmax_bwd_f32": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P]),

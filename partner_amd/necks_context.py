@@ -11,6 +11,11 @@ Execution: the row pieces are gathered into one padded NHWC map by ``pn_assemble
 is the H axis of the NHWC maps) and the convolution runs on the MFMA kernel with padding 0 along the azimuth and 1 along the
 range.  ``mode='feature_only'`` with several sectors reproduces the reference's indexing literally (rpn_context.py:117-124),
 including the fact that its entry 0 is built from sector 1.
+
+The streaming pass reads ``padding`` rows of the previous sweep at every sector border and nothing else of it, so ``prev_sweep`` may
+hold, per layer, a ``PrevStrips`` pack of exactly those rows (``strip_rows`` / ``strip_sources``; `pn_polar_warp_strips_f32` writes
+them for all layers in one launch) in place of the whole warped map, and the ``feature_only`` pass that feeds it may stop at the last
+layer's input (``inputs_only``).
 """
 from __future__ import annotations
 
@@ -121,6 +126,38 @@ class _DeblockOnly:
         self.blocks, self.deblocks, self._fused = [], neck.deblocks, RPN._fused
 
 
+def strip_rows(nsectors: int, hs: int, pad: int):
+    """the whole-sweep rows (h = nsectors * hs) a strip pack holds, strip by strip: strip k < nsectors = rows [k * hs, k * hs + pad), the
+    head of sector k; strip nsectors = rows [h - pad, h), the tail of the last sector (`pn_polar_warp_strips_f32`)"""
+    assert nsectors >= 1 and 1 <= pad <= hs
+    return [list(range(k * hs, k * hs + pad)) for k in range(nsectors)] + [list(range(nsectors * hs - pad, nsectors * hs))]
+
+
+def strip_sources(nsectors: int, sec_id: int):
+    """(strip feeding the TOP edge, strip feeding the BOTTOM edge) of sector ``sec_id`` in the streaming pass, None where the edge takes
+    no row of the previous sweep (the trailing edge of sectors > 0 comes from the sector before; one sector pads circularly):
+    top of sector 0 = the last strip (the sweep's last rows), lead of sector j = strip j + 1 (the head of sector j + 1), bottom of the
+    last sector = strip 0 (the sweep's first rows)"""
+    if nsectors == 1:
+        return None, None
+    return (nsectors if sec_id == 0 else None), (sec_id + 1 if sec_id < nsectors - 1 else 0)
+
+
+class PrevStrips:
+    """The previous sweep's warped rows of ONE layer as the streaming pass reads them: ``rows`` (bs, (nsectors + 1) * pad, w, c) NHWC, the
+    strips of ``strip_rows(nsectors, hs, pad)`` in that order; stands where the whole warped map (bs, nsectors * hs, w, c) stood."""
+
+    def __init__(self, rows: torch.Tensor, nsectors: int, pad: int, hs: int):
+        assert rows.dim() == 4 and rows.shape[1] == (nsectors + 1) * pad and 1 <= pad <= hs
+        self.rows, self.nsectors, self.pad, self.hs = rows, int(nsectors), int(pad), int(hs)
+
+    def piece(self, sample: int, strip: int, p: int):
+        """the ``p <= pad`` rows of ``strip`` that touch the border as an ``ops.assemble_rows`` piece: the first rows of a sector's head,
+        the last rows of the sweep's tail"""
+        assert p <= self.pad
+        return (self.rows, sample, strip * self.pad + (self.pad - p if strip == self.nsectors else 0), p)
+
+
 @NECKS.register_module
 class RPNBDCP(RPNTECP):
     """RPN with bidirectional padding (rpn_context.py:160-215)"""
@@ -160,38 +197,59 @@ class RPNBDCP(RPNTECP):
     def _pad_streaming(self, layer, x, prev_sweep, prev, sec_id):
         p = layer["padding"]
         n, h, w, c = x.shape
-        full = prev_sweep.shape[1]
-        nsec = full // h
+        if isinstance(prev_sweep, PrevStrips):      # the border rows alone: the same pieces, taken from the strip pack
+            nsec = prev_sweep.nsectors
+            assert prev_sweep.hs == h or nsec == 1, "the strip pack was cut for another sector height"
+            top_strip, bottom_strip = strip_sources(nsec, sec_id)
+            lead = lambda k: prev_sweep.piece(k, bottom_strip, p)  # noqa: E731
+            sweep_top = lambda k: prev_sweep.piece(k, top_strip, p)  # noqa: E731
+            sweep_bottom = lead
+        else:
+            full = h if prev_sweep is None else prev_sweep.shape[1]      # None: one sector, nothing of the previous sweep is read
+            nsec = full // h
+            lead = lambda k: (prev_sweep, k, (sec_id + 1) * h, p)  # noqa: E731
+            sweep_top = lambda k: (prev_sweep, k, full - p, p)  # noqa: E731
+            sweep_bottom = lambda k: (prev_sweep, k, 0, p)  # noqa: E731
         if nsec == 1:
             return layer["ctx"](ops.assemble_rows([[(x, k, h - p, p), (x, k, 0, h), (x, k, 0, p)] for k in range(n)], w, c)), prev
-        lead = lambda k: (prev_sweep, k, (sec_id + 1) * h, p)  # noqa: E731
         if sec_id == 0:
-            top = (lambda k: (prev_sweep, k, full - p, p)) if layer["mod"].nsectors == nsec else (lambda k: (None, p))
+            top = sweep_top if layer["mod"].nsectors == nsec else (lambda k: (None, p))
             samples = [[top(k), (x, k, 0, h), lead(k)] for k in range(n)]
         elif sec_id == nsec - 1:
             ctx = prev.pop(0)
-            bottom = (lambda k: (prev_sweep, k, 0, p)) if layer["mod"].nsectors == nsec else (lambda k: (None, p))
+            bottom = sweep_bottom if layer["mod"].nsectors == nsec else (lambda k: (None, p))
             samples = [[(ctx, k, ctx.shape[1] - p, p), (x, k, 0, h), bottom(k)] for k in range(n)]
         else:
             ctx = prev.pop(0)
             samples = [[(ctx, k, ctx.shape[1] - p, p), (x, k, 0, h), lead(k)] for k in range(n)]
         return layer["ctx"](ops.assemble_rows(samples, w, c)), prev
 
-    def forward_nhwc(self, x, prev_sweep=(), prev_context=(), sec_id=0, nsectors=1, mode="feature_only"):
+    def forward_nhwc(self, x, prev_sweep=(), prev_context=(), sec_id=0, nsectors=1, mode="feature_only", inputs_only=False):
+        """``prev_sweep`` (streaming modes): per layer the previous sweep's warped whole map, or a ``PrevStrips`` pack of its border rows;
+        with one sector it may be empty (the padding is circular, nothing of it is read).  ``inputs_only`` (``feature_only``): stop once
+        the last layer's input is recorded -- no last convolution, no deblocks -- and return (None, the layers' inputs)."""
         eval_only(self, "RPNBDCP")
         plan = self._plan.get(self, self._build_plan)
         prev = list(prev_context)
         cur, out, off, layer_id = [], None, 0, 0
+        assert not inputs_only or mode == "feature_only", "inputs_only belongs to the feature_only pass"
+        nlayers = sum(len(layers) for layers in plan["blocks"])
         for i, layers in enumerate(plan["blocks"]):
             for layer in layers:
                 cur.append(x)                                        # the whole input of the layer (rpn_context.py:114)
+                if inputs_only and len(cur) == nlayers:
+                    return None, cur
                 if mode == "feature_only":
                     x = self._pad_feature_only(layer, x, nsectors)
+                elif len(prev_sweep) == 0:
+                    assert nsectors == 1, "several sectors stream against the previous sweep's maps"
+                    x, prev = self._pad_streaming(layer, x, None, prev, sec_id)
                 else:
                     ps = prev_sweep[layer_id]
                     layer_id = (layer_id + 1) % len(prev_sweep)
                     x, prev = self._pad_streaming(layer, x, ps, prev, sec_id)
-            out, off = self._deblocks(plan, i, x, out, off)
+            if not inputs_only:
+                out, off = self._deblocks(plan, i, x, out, off)
         return (out if out is not None else x), cur
 
     def forward(self, x, prev_sweep=[], prev_context=[], sec_id=0, nsectors=1, mode="feature_only"):

@@ -102,7 +102,8 @@ class SingleConvHead(nn.Module):
             assert base.stride(2) == 1 and base.stride(1) == cstride
             if cstride != ncls:                                  # padded buffer: compact once (small: H*W*ncls floats)
                 base = base.contiguous()
-            hip.call("pn_seg_point_labels", base.data_ptr(), h, w, ncls, gi.data_ptr(), gi.shape[0], labels.data_ptr(), hip.stream())
+            if gi.shape[0]:                                      # a sample without points in this sector (streaming): an empty label tensor
+                hip.call("pn_seg_point_labels", base.data_ptr(), h, w, ncls, gi.data_ptr(), gi.shape[0], labels.data_ptr(), hip.stream())
             meta = example["metadata"][i]
             token = meta["token"] if isinstance(meta, dict) and "token" in meta else i
             out.append({token: labels})
