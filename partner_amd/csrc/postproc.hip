@@ -7,8 +7,10 @@
 // Pipeline per sample, all on the caller's stream, no host round trip:
 //   decode_kernel        every cell: sigmoid/max over classes, exp(dim), atan2(rot), polar cell centre -> Cartesian,
 //                        score / range mask
-//   select_sort_kernel   one block: order-preserving compaction of the valid cells into LDS (cap 8192), bitonic sort
-//                        by (score desc, cell asc) -- torch.sort leaves ties unspecified --, first pre_max survive
+//   select_sort_kernel   one block: histogram cuts on the score bits narrow the valid cells down to a superset of the best pre_max
+//                        (12 + 12 bits; all 31 when more than 8192 cells still tie on those), compaction into LDS (cap 8192), bitonic
+//                        sort by (score desc, cell asc) -- torch.sort leaves ties unspecified --, first pre_max survive: the same
+//                        selection and order as a full sort of every valid cell
 //   nms_mask_kernel      64 x 64 IoU tiles -> suppression bit masks (same tiling as the reference)
 //   nms_reduce_kernel    one wave walks the sorted boxes, lane l owns word l of the "removed" bit set
 //   gather_kernel        kept[:post_max] -> box3d_lidar / scores / label_preds
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(kSortThreads) void select_sort_kernel(const float* 
   int* hist = reinterpret_cast<int*>(sort_lds + kCap);       // [kHistBins]
   __shared__ int wave_cnt[kSortThreads / 64];
   __shared__ int chunk_tot[kHistBins / 64];
-  __shared__ int n_valid, cut_bin, n_ge, n_kept, sub_cut;
+  __shared__ int n_valid, cut_bin, n_ge, n_kept, sub_cut, low_cut, n_ge_low;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float* sc = score + (size_t)b * cells;
   SORT_STAMP(0);
@@ -358,14 +360,39 @@ __global__ __launch_bounds__(kSortThreads) void select_sort_kernel(const float* 
       }
     }
   } else {
-    // still too many: more than kCap scores agree in their top 24 bits.  First everything strictly above the refined cut, then
-    // the refined cut bin itself in cell order until the sort buffer is full (ordered compaction, block scans).
+    // still too many: more than kCap scores agree in their top 24 bits (the refinement above always ran: refine_above <= kCap).  Scores of
+    // that sub-bin may still differ in their low 7 bits, so a third histogram, over those bits of the sub-bin's entries, finds the very
+    // score -- all 31 bits -- in which the pre_max-th best falls.  First everything strictly above that score (fewer than pre_max
+    // entries), then the entries EQUAL to it in cell order until the sort buffer is full (ordered compaction, block scans): exact ties
+    // rank by ascending cell, so the first of them in cell order are the ones the full sort would keep.
+    const int n_above_sub = n_ge - hist[scut];   // strictly above the refined sub-bin: fewer than pre_max by construction
+    const int n_in_sub = n_ge - n_above_sub;
+    __syncthreads();
+    for (int i = tid; i < kHistBins; i += kSortThreads) hist[i] = 0;
+    __syncthreads();
+    const unsigned sub_key = (cut << 12) | scut;   // score bits [30:7] of the sub-bin (valid scores have a clear sign bit)
+    for (int c0 = 0; c0 < cells; c0 += kSortThreads * kBatch) {
+      float sv[kBatch];
+#pragma unroll
+      for (int k = 0; k < kBatch; ++k) {
+        const int c = c0 + k * kSortThreads + tid;
+        sv[k] = c < cells ? sc[c] : -1.f;
+      }
+#pragma unroll
+      for (int k = 0; k < kBatch; ++k) {
+        const unsigned u = __builtin_bit_cast(unsigned, sv[k]) & 0x7fffffffu;
+        if (sv[k] >= 0.f && (u >> 7) == sub_key) atomicAdd(&hist[u & 127u], 1);
+      }
+    }
+    __syncthreads();
+    find_cut(pre_max - n_above_sub, n_in_sub, &low_cut, &n_ge_low);
+    const unsigned cut_score = (sub_key << 7) | (unsigned)low_cut;   // positive floats order like their bits
     for (int phase = 0; phase < 2; ++phase)
       for (int c0 = 0; c0 < cells; c0 += kSortThreads) {
         const int c = c0 + tid;
         const float s = c < cells ? sc[c] : -1.f;
-        const unsigned u = __builtin_bit_cast(unsigned, s), bin = (u >> 19) & (kHistBins - 1), sub = (u >> 7) & (kHistBins - 1);
-        const bool above = bin > cut || (bin == cut && sub > scut), equal = bin == cut && sub == scut;
+        const unsigned u = __builtin_bit_cast(unsigned, s) & 0x7fffffffu;
+        const bool above = u > cut_score, equal = u == cut_score;
         const bool v = s >= 0.f && (phase == 0 ? above : equal);
         const unsigned long long bal = __ballot(v);
         if (lane == 0) wave_cnt[wv] = __popcll(bal);
