@@ -822,6 +822,38 @@ int pn_bilinear_upsample_add_f32(const float *low, int batch, int h, int w, int 
                                  float *out, pn_stream_t stream);
 int pn_seg_point_labels(const float *seg_sample, int h, int w, int classes, const int64_t *grid_ind,
                         int n, int64_t *labels, pn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Training of the seg super-task.
+ *
+ * pn_bilinear_upsample_add_bwd_f32: d_low (B,h,w,C) = the exact adjoint of pn_bilinear_upsample_add_f32 applied to d_out (B,H,W,C)
+ * (autograd of F.interpolate(mode='bilinear', align_corners=False) in SingleConvHead.forward, seg_head.py:75-83), for every size pair
+ * the forward accepts.  Gather form: every low-resolution cell sums its contributions in a fixed order (no atomics); d_low is
+ * overwritten.
+ *
+ * pn_seg_loss_f32: SegLoss.forward (det3d/models/losses/seg_loss.py:19-22) = lovasz_softmax(softmax(logits), labels, ignore)
+ * (lovasz_losses.py:160-229 with classes='present', flatten_probas; lovasz_grad :24-36) + nn.CrossEntropyLoss(ignore_index=ignore),
+ * and its gradient (what autograd computes for the reference).
+ *   logits   NHWC, `cells` = B*H*W rows of `classes` (<= 32) floats with `pixel_stride` floats between rows, read in place
+ *   labels   DEVICE int64 (labels_int64 != 0) or int32, one per cell; a cell is valid when its label != ignore and lies in [0, classes)
+ *   max_valid  capacity for the valid cells (<= 0 or >= cells: cells).  More valid cells than that: *status = 1, out[0..2] = NaN,
+ *            dlogits = 0 -- decided on the device, nothing is read back
+ *   out[5]   DEVICE [loss, lovasz, ce, n_valid, n_present]; no valid cell: loss = 0 (the reference returns an empty tensor + NaN)
+ *   status   DEVICE int32 (may be NULL)
+ *   dlogits  d(scale * loss)/d(logits) in the logits' layout, zero at ignored cells and in the pad channels; NULL: value only
+ * Descending stable order of the errors (ties by ascending valid-cell index), integer scans of the foreground flags, fixed-order f64
+ * partial sums: bit-reproducible.  Workspace: pn_seg_loss_workspace_bytes(cells, classes, max_valid), 256-byte aligned.
+ * pn_seg_loss_tile_elems(which): 0 = keys per tile of the compaction / radix sort / scan, 1 = threads per block, 2 = keys ranked per
+ * step of the scatter (the sizes at which the kernels change path; the tests place P around them).
+ */
+int pn_bilinear_upsample_add_bwd_f32(const float *d_out, int batch, int h, int w, int c, int out_h, int out_w,
+                                     float *d_low, pn_stream_t stream);
+int pn_seg_loss_tile_elems(int which);
+size_t pn_seg_loss_workspace_bytes(long long cells, int classes, long long max_valid);
+int pn_seg_loss_f32(const float *logits, int pixel_stride, long long cells, int classes, const void *labels,
+                    int labels_int64, long long ignore, long long max_valid, float scale, float *out,
+                    int32_t *status, float *dlogits, void *workspace, size_t workspace_bytes,
+                    pn_stream_t stream);
 /* Panoptic fusion of one sample (SingleConvHead.predict_panoptic, seg_head.py:99-168): pn_seg_point_labels fused with the
  * nearest-box search, one launch writing labels[n] and instance[n] (both int64).  seg_sample: the sample's logits (h, w, classes)
  * with pixel_stride floats between pixels (a padded NHWC buffer is read in place).  points: the sample's first row, point_stride

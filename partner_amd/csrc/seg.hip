@@ -40,6 +40,50 @@ __global__ void bilinear_up_add_kernel(const float* __restrict__ low, int B, int
   }
 }
 
+// d_low (B,h,w,C) = adjoint of bilinear_up_add_kernel applied to d_out (B,H,W,C), gather form: one thread per low-resolution cell and
+// channel group walks the output pixels that can read the cell, recomputes the forward's source coordinates and weights with the
+// forward's own f32 operations, and sums its contributions in a fixed (Y, X) order -- no atomics, bit-reproducible.  Output row Y reads
+// low rows y0 = floor(fy) and y1 = min(y0 + 1, h - 1), so cell y is read by the rows with fy in [y - 1, y + 1) (plus the rows clamped to
+// 0 below); the walked range is that interval with a pixel of margin either side, the exact test is on y0 / y1.
+__global__ void bilinear_up_add_bwd_kernel(const float* __restrict__ d_out, int B, int h, int w, int C, int H, int W, float* __restrict__ d_low) {
+  const int c4n = C / 4;
+  const size_t total = (size_t)B * h * w * c4n;
+  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % c4n);
+    size_t p = i / c4n;
+    const int x = (int)(p % w); p /= w;
+    const int y = (int)(p % h);
+    const int b = (int)(p / h);
+    const int Y_lo = max(0, (int)floorf(((float)y - 0.5f) / sy - 0.5f) - 1), Y_hi = min(H - 1, (int)ceilf(((float)y + 1.5f) / sy - 0.5f) + 1);
+    const int X_lo = max(0, (int)floorf(((float)x - 0.5f) / sx - 0.5f) - 1), X_hi = min(W - 1, (int)ceilf(((float)x + 1.5f) / sx - 0.5f) + 1);
+    const float4* src = reinterpret_cast<const float4*>(d_out) + (size_t)b * H * W * c4n;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int Y = Y_lo; Y <= Y_hi; ++Y) {
+      float fy = ((float)Y + 0.5f) * sy - 0.5f;
+      fy = fy < 0.f ? 0.f : fy;
+      const int y0 = (int)fy, y1 = y0 + (y0 < h - 1 ? 1 : 0);
+      const float ly = fy - (float)y0, hy = 1.f - ly;
+      const float wy = (y0 == y ? hy : 0.f) + (y1 == y ? ly : 0.f);
+      if (y0 != y && y1 != y) continue;
+      for (int X = X_lo; X <= X_hi; ++X) {
+        float fx = ((float)X + 0.5f) * sx - 0.5f;
+        fx = fx < 0.f ? 0.f : fx;
+        const int x0 = (int)fx, x1 = x0 + (x0 < w - 1 ? 1 : 0);
+        if (x0 != x && x1 != x) continue;
+        const float lx = fx - (float)x0, hx = 1.f - lx;
+        const float wt = wy * ((x0 == x ? hx : 0.f) + (x1 == x ? lx : 0.f));
+        const float4 g = src[((size_t)Y * W + X) * c4n + c4];
+        acc.x += wt * g.x;
+        acc.y += wt * g.y;
+        acc.z += wt * g.z;
+        acc.w += wt * g.w;
+      }
+    }
+    reinterpret_cast<float4*>(d_low)[i] = acc;
+  }
+}
+
 // label of point i = 1 + argmax_c seg[b, y, x, c] at the point's BEV cell (first maximum, as torch.argmax);
 // grid_ind rows are [z, y(theta), x(r)] as the reference's valid_grid_ind (seg_head.py:186-192, 2-D prediction map)
 __global__ void seg_point_labels_kernel(const float* __restrict__ seg, int H, int W, int C, const int64_t* __restrict__ grid_ind, int n,
@@ -214,6 +258,16 @@ int pn_bilinear_upsample_add_f32(const float* low, int batch, int h, int w, int 
   hipLaunchKernelGGL(bilinear_up_add_kernel, dim3((unsigned)std::min<size_t>(8192, (total + 255) / 256)), dim3(256), 0, pn::S(stream), low, batch,
                      h, w, c, out_h, out_w, out);
   return pn::check_launch("bilinear_up_add_kernel");
+}
+
+int pn_bilinear_upsample_add_bwd_f32(const float* d_out, int batch, int h, int w, int c, int out_h, int out_w, float* d_low, pn_stream_t stream) {
+  PN_REQUIRE(d_out && d_low && batch >= 1 && h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1, "bilinear_upsample_add_bwd: bad arguments");
+  PN_REQUIRE(c >= 4 && c % 4 == 0 && ((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_low & 15) == 0,
+             "bilinear_upsample_add_bwd: channel count must be a multiple of 4 and the maps 16-byte aligned");
+  const size_t total = (size_t)batch * h * w * (c / 4);
+  hipLaunchKernelGGL(bilinear_up_add_bwd_kernel, dim3((unsigned)std::min<size_t>(8192, (total + 255) / 256)), dim3(256), 0, pn::S(stream), d_out, batch,
+                     h, w, c, out_h, out_w, d_low);
+  return pn::check_launch("bilinear_up_add_bwd_kernel");
 }
 
 int pn_seg_point_labels(const float* seg_sample, int h, int w, int classes, const int64_t* grid_ind, int n, int64_t* labels, pn_stream_t stream) {

@@ -224,9 +224,10 @@ class PointPillars(SingleStageDetector):
     def forward(self, example, return_loss=True, **kwargs):
         preds = self.extract_preds(example)
         if return_loss:
-            if self.seg_head is not None:
-                raise NotImplementedError("training with the segmentation head is out of scope (SegLoss is not built)")
-            return self.bbox_head.loss(example, preds)
+            losses = self.bbox_head.loss(example, preds)
+            if self.seg_head is not None:      # point_pillars.py:99-103: both super-tasks' terms in one dict
+                losses.update(self.seg_head.loss(example, preds))
+            return losses
         if kwargs.get("raw_preds", False) or self.test_cfg is None:
             return preds
         ret = {}

@@ -1,10 +1,15 @@
 """Segmentation head of the reference's nuScenes polar config (`super_tasks = ['det', 'seg']`): SingleConvHead
-(det3d/models/seg_heads/seg_head.py:53-83, 99-168, 176-195) and its loss object SegLoss (det3d/models/losses/seg_loss.py:8-22).
-Secondary to the detection hot path: forward, per-point prediction and the panoptic fusion with the detection boxes run on the HIP
-kernels (eval); the loss (Lovasz softmax + cross entropy) is not built."""
+(det3d/models/seg_heads/seg_head.py:53-96, 99-168, 176-195), its label helper ``get_labels`` (seg_head.py:24-49) and its loss object
+SegLoss (det3d/models/losses/seg_loss.py:8-22).  Secondary to the detection hot path.  Forward, per-point prediction and the panoptic
+fusion with the detection boxes run on the HIP kernels (eval).  Training: SegLoss = Lovasz softmax + cross entropy with its gradient
+(csrc/seg_loss.hip: device-resident compaction, segmented radix sort, integer scans; nothing is read back), ``SingleConvHead.loss``, and
+``SegHeadTrain``, the head's explicit forward / backward (1x1 convolutions, the bilinear up-sampling and its adjoint) that
+``train.PolarPillarTrainStep`` drives.  Not built: the pooled down-sampling branch of ``get_labels`` (seg_head.py:33-49)."""
 from __future__ import annotations
 
+import ctypes as C
 import math
+from typing import Optional
 
 import torch
 from torch import nn
@@ -18,16 +23,228 @@ from .nn_utils import PlanCache, eval_only
 SEMANTIC2BOX = ["barrier", "bicycle", "bus", "car", "construction_vehicle", "motorcycle", "pedestrian", "traffic_cone", "trailer", "truck"]
 
 
+def seg_loss_sizes() -> dict:
+    """the sizes at which the loss kernels change path: keys per tile of the compaction / radix sort / scan, threads per block, keys ranked
+    per step of the radix scatter (one wave)"""
+    lib = hip.load()
+    return dict(tile=lib.pn_seg_loss_tile_elems(0), block=lib.pn_seg_loss_tile_elems(1), chunk=lib.pn_seg_loss_tile_elems(2))
+
+
+def get_labels(labels: torch.Tensor, pred_shape) -> torch.Tensor:
+    """semantic labels for the loss from ``voxel_labels`` (0 = unlabelled): equal shapes -> ``labels - 1`` (seg_head.py:30-32; hence the
+    config's ``ignore=-1``).  The pooled down-sampling of labels larger than the prediction (seg_head.py:33-49) is not built."""
+    if tuple(labels.shape[1:]) == tuple(pred_shape):
+        return labels - 1
+    raise NotImplementedError(f"get_labels: labels {tuple(labels.shape[1:])} against predictions {tuple(pred_shape)} -- the pooled "
+                              "down-sampling branch of get_labels (seg_head.py:33-49) is not built")
+
+
+def seg_loss_nhwc(logits: torch.Tensor, pixel_stride: int, num_classes: int, labels: torch.Tensor, ignore: int, scale: float = 1.0,
+                  max_valid: Optional[int] = None, want_grad: bool = True):
+    """`pn_seg_loss_f32` on logits stored as rows of ``pixel_stride`` floats per cell (an NHWC buffer with padded channels, read in
+    place; ``logits`` is any tensor whose data pointer is the first row).  labels: device int32 / int64, one per cell in (b, y, x) order.
+    -> (vec (5,) [loss, lovasz, ce, n_valid, n_present], dlogits (cells, pixel_stride) = d(scale * loss)/d(logits) or None,
+    status (1,) int32: 1 when more than ``max_valid`` cells are labelled).  All on the device, nothing is read back."""
+    hip.require_device(logits, labels)
+    assert logits.dtype == torch.float32
+    if labels.dtype not in (torch.int32, torch.int64):
+        labels = labels.to(torch.int64)
+    labels = labels.contiguous()
+    cells = labels.numel()
+    dev = logits.device
+    lib = hip.load()
+    cap = int(max_valid) if max_valid is not None else 0
+    nbytes = lib.pn_seg_loss_workspace_bytes(cells, num_classes, cap)
+    if nbytes == 0:
+        raise hip.PartnerHipError(f"seg_loss: unsupported sizes (cells {cells}, classes {num_classes})")
+    ws = ops._workspace(nbytes, dev)
+    vec = torch.empty(5, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    dlogits = torch.empty((cells, pixel_stride), dtype=torch.float32, device=dev) if want_grad else None
+    hip.call("pn_seg_loss_f32", logits.data_ptr(), int(pixel_stride), cells, int(num_classes), labels.data_ptr(), int(labels.dtype == torch.int64),
+             int(ignore), cap, float(scale), vec.data_ptr(), status.data_ptr(), hip.ptr(dlogits), ws.data_ptr(), nbytes, hip.stream())
+    return vec, dlogits, status
+
+
+def bilinear_upsample_add_bwd(d_out: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """d_low (B,h,w,C) = adjoint of ``pn_bilinear_upsample_add_f32`` applied to d_out (B,H,W,C) NHWC, C a multiple of 4"""
+    hip.require_device(d_out)
+    assert d_out.dim() == 4 and d_out.is_contiguous() and d_out.dtype == torch.float32
+    b, hh, ww, c = d_out.shape
+    d_low = torch.empty((b, h, w, c), dtype=torch.float32, device=d_out.device)
+    hip.call("pn_bilinear_upsample_add_bwd_f32", d_out.data_ptr(), b, h, w, c, hh, ww, d_low.data_ptr(), hip.stream())
+    return d_low
+
+
 @LOSSES.register_module
 class SegLoss(nn.Module):
-    """parameter-free; kept so that the config's ``loss=dict(type='SegLoss', ignore=-1)`` builds"""
+    """lovasz_softmax(softmax(outputs), labels, ignore) + CrossEntropyLoss(ignore_index=ignore) (seg_loss.py:19-22), parameter-free.
+
+    Departures from the reference, which is broken there: no valid cell -> loss 0 and a zero gradient (the reference returns an empty
+    tensor + NaN); one valid cell -> the formula is evaluated (the reference raises in flatten_probas).  Equal errors are ordered by
+    ascending cell index (the reference's torch.sort is unstable)."""
 
     def __init__(self, ignore=0):
         super().__init__()
         self.ignore = ignore
 
-    def forward(self, outputs, labels):
-        raise NotImplementedError("SegLoss (Lovasz softmax + cross entropy, seg_loss.py:19-22) is not built: segmentation training is out of scope")
+    @staticmethod
+    def _rows(outputs: torch.Tensor):
+        """logical (B,C,H,W) -> (tensor whose data pointer is the first NHWC row, pixel stride): a channels-last view -- the head's
+        channel-padded buffer included -- is read in place, anything else is copied to NHWC once"""
+        assert outputs.dim() == 4 and outputs.dtype == torch.float32
+        b, c, h, w = outputs.shape
+        st = outputs.stride()
+        if (c == 1 or st[1] == 1) and st[3] >= c and st[2] == w * st[3] and (b == 1 or st[0] == h * st[2]):
+            return outputs, st[3]
+        return ops.to_nhwc(outputs), c
+
+    def loss_and_grad(self, outputs: torch.Tensor, labels: torch.Tensor, scale: float = 1.0, max_valid: Optional[int] = None):
+        """-> (loss vector (5,) [loss, lovasz, ce, n_valid, n_present], dlogits (B,H,W,pixel stride) = d(scale * loss)/d(logits) in the
+        layout of the logits' NHWC buffer), both on the device (the training step's entry: no autograd, no readback)"""
+        b, c, h, w = outputs.shape
+        assert tuple(labels.shape) == (b, h, w), "labels must be (B, H, W)"
+        rows, stride = self._rows(outputs)
+        vec, dlogits, _ = seg_loss_nhwc(rows, stride, c, labels, self.ignore, scale, max_valid)
+        return vec, dlogits.view(b, h, w, stride)
+
+    def forward(self, outputs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """outputs (B,C,H,W) logits, labels (B,H,W) integer -> the loss, a device scalar"""
+        b, c, h, w = outputs.shape
+        assert tuple(labels.shape) == (b, h, w), "labels must be (B, H, W)"
+        rows, stride = self._rows(outputs)
+        return seg_loss_nhwc(rows, stride, c, labels, self.ignore, want_grad=False)[0][0]
+
+
+class SegHeadTrain:
+    """SingleConvHead's training forward and explicit backward (kernel = 1), without autograd:
+      logits = conv(x1; W[:, :C1]) + bias + bilinear_up(conv(x2; W[:, C1:]))
+    ``weight`` / ``bias`` / ``grad_weight`` / ``grad_bias`` default to the head's parameters and fresh gradient tensors; the training
+    step passes the views of its flat buffers.  ``side``: ops.SideStream for the weight-gradient launches.
+
+    ``forward(x1, x2, vi=None)``: with ``vi`` (the iteration's VoxelIndex) x1 is a canvas of which only the pillars' cells are valid
+    (the pillar-features first layer builds no dense canvas): the canvas part of the logits is then computed on the pillar rows and
+    scattered, and the bias rides on the low-resolution term (interpolation weights sum to one)."""
+
+    def __init__(self, head: "SingleConvHead", weight=None, bias=None, grad_weight=None, grad_bias=None, side=None):
+        if head.conv.kernel_size != (1, 1):
+            raise NotImplementedError("SegHeadTrain: only kernel=1 (the reference config) has a HIP path")
+        self.head, self.n = head, head.num_classes
+        self.npad = (self.n + 3) // 4 * 4
+        self.w = head.conv.weight.detach() if weight is None else weight
+        self.b = head.conv.bias.detach() if bias is None else bias
+        hip.require_device(self.w, self.b)
+        self.gw = torch.zeros_like(self.w) if grad_weight is None else grad_weight
+        self.gb = torch.zeros_like(self.b) if grad_bias is None else grad_bias
+        self.side = side
+        self._plan = None
+        self.x1 = self.x2 = self.vi = self.rows = self._d_rows = None
+
+    def _layers(self, c1: int, rows: bool):
+        """the packed layers of one form, refreshed from the current parameters; ``rows``: the bias rides on the low-resolution term"""
+        n, npad, dev = self.n, self.npad, self.w.device
+        p = self._plan
+        if p is None or (p["c1"], p["rows"]) != (c1, rows):
+            wa = torch.zeros((npad, c1, 1, 1), dtype=torch.float32, device=dev)
+            wb = torch.zeros((npad, self.w.shape[1] - c1, 1, 1), dtype=torch.float32, device=dev)
+            bias = torch.zeros((npad,), dtype=torch.float32, device=dev)
+            p = self._plan = dict(c1=c1, rows=rows, wa=wa, wb=wb, bias=bias, a=ops.ConvLayer(wa, shift=None if rows else bias, act=ops.ACT_NONE),
+                                  b=ops.ConvLayer(wb, shift=bias if rows else None, act=ops.ACT_NONE), da=ops.ConvDgrad(wa, 1, 0), db=ops.ConvDgrad(wb, 1, 0))
+        p["wa"][:n].copy_(self.w[:, :c1])
+        p["wb"][:n].copy_(self.w[:, c1:])
+        p["bias"][:n].copy_(self.b)
+        p["a"].repack(p["wa"], None if rows else p["bias"])
+        p["b"].repack(p["wb"], p["bias"] if rows else None)
+        p["da"].repack(p["wa"])
+        p["db"].repack(p["wb"])
+        return p
+
+    def _dims(self, x1):
+        return (C.c_int32 * 4)(x1.shape[0], 1, x1.shape[1], x1.shape[2])
+
+    def forward(self, x1: torch.Tensor, x2: torch.Tensor, vi=None) -> torch.Tensor:
+        """x1 (B,H,W,C1), x2 (B,h,w,C2) NHWC -> logits (B,H,W,npad) NHWC; keeps what backward needs"""
+        hip.require_device(x1, x2)
+        assert x1.shape[3] + x2.shape[3] == self.w.shape[1], "channel split does not match in_channels"
+        p = self._layers(x1.shape[3], vi is not None)
+        self.x1, self.x2, self.vi, self.rows, self._d_rows = x1, x2, vi, None, None
+        st = hip.stream()
+        if vi is None:
+            out = p["a"](x1)
+            low = p["b"](x2)
+        else:
+            b, h, w, c1 = x1.shape
+            cap = max(vi.n_cap, 1)
+            self.rows = torch.zeros((1, 1, cap, c1), dtype=torch.float32, device=x1.device)        # rows past the voxel count stay zero
+            hip.call("pn_sparse_from_dense_nhwc", x1.data_ptr(), vi.unq_keys_ptr, cap, vi.num_voxels.data_ptr(), self._dims(x1), c1, self.rows.data_ptr(), st)
+            row_logits = p["a"](self.rows)
+            out = torch.empty((b, h, w, self.npad), dtype=torch.float32, device=x1.device)
+            hip.call("pn_sparse_to_dense_nhwc", row_logits.data_ptr(), vi.unq_keys_ptr, cap, vi.num_voxels.data_ptr(), self._dims(x1), self.npad, out.data_ptr(), st)
+            low = p["b"](x2)
+        hip.call("pn_bilinear_upsample_add_f32", low.data_ptr(), low.shape[0], low.shape[1], low.shape[2], low.shape[3], out.shape[1], out.shape[2],
+                 out.data_ptr(), st)
+        return out
+
+    def _on_side(self, fn, *reads):
+        if self.side is not None:
+            self.side.run(fn, *reads)
+        else:
+            fn()
+
+    def backward_x2(self, dlogits: torch.Tensor, d_x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the low-resolution half: d(x2) (added into ``d_x2`` when given) and the gradients of W[:, C1:] and the bias"""
+        p, n = self._plan, self.n
+        d_low = bilinear_upsample_add_bwd(dlogits, self.x2.shape[1], self.x2.shape[2])
+        x2, c1 = self.x2, p["c1"]
+
+        def weight_grads():
+            g = ops.conv_wgrad(x2, d_low, 1, 1, 1, 0, cout=n)
+            self.gw[:, c1:].copy_(g)
+            ops.channel_sum(dlogits, c=n, out=self.gb)
+
+        self._on_side(weight_grads, d_low, x2, dlogits)
+        return p["db"](d_low, out=d_x2, accumulate=d_x2 is not None)
+
+    def _canvas_operands(self, dlogits: torch.Tensor):
+        """(input, output gradient) of the canvas-half convolution: the dense maps, or after a forward with ``vi`` the pillar rows"""
+        if self.vi is None:
+            return self.x1, dlogits
+        if self._d_rows is None:
+            vi, cap = self.vi, max(self.vi.n_cap, 1)
+            self._d_rows = torch.zeros((1, 1, cap, self.npad), dtype=torch.float32, device=dlogits.device)
+            hip.call("pn_sparse_from_dense_nhwc", dlogits.data_ptr(), vi.unq_keys_ptr, cap, vi.num_voxels.data_ptr(), self._dims(self.x1), self.npad,
+                     self._d_rows.data_ptr(), hip.stream())
+        return self.rows, self._d_rows
+
+    def backward_x1(self, dlogits: torch.Tensor, need_dx: bool = True):
+        """the canvas half: the gradient of W[:, :C1] and (``need_dx``) d(x1) -- the dense (B,H,W,C1) canvas gradient, or, after a forward
+        with ``vi``, the (n_cap, C1) pillar-feature gradient"""
+        n, c1 = self.n, self._plan["c1"]
+        x, d = self._canvas_operands(dlogits)
+
+        def weight_grads():
+            g = ops.conv_wgrad(x, d, 1, 1, 1, 0, cout=n)
+            self.gw[:, :c1].copy_(g)
+
+        self._on_side(weight_grads, d, x)
+        if not need_dx:
+            return None
+        res = self._plan["da"](d)
+        return res if self.vi is None else res.view(-1, c1)
+
+    def backward_canvas(self, dlogits: torch.Tensor, d_x1: torch.Tensor) -> torch.Tensor:
+        """d(x1) ADDED into ``d_x1``: a dense canvas gradient, or (forward with ``vi``) the (n_cap, C1) pillar-feature gradient"""
+        x, d = self._canvas_operands(dlogits)
+        self._plan["da"](d, out=d_x1.view(x.shape), accumulate=True)
+        return d_x1
+
+    def backward(self, dlogits: torch.Tensor):
+        """-> (d_x1, d_x2); the parameter gradients land in ``gw`` / ``gb``"""
+        d_x2 = self.backward_x2(dlogits)
+        d_x1 = self.backward_x1(dlogits)
+        if self.side is not None:
+            self.side.join()
+        return d_x1, d_x2
 
 
 @SEG_HEAD.register_module
@@ -75,7 +292,13 @@ class SingleConvHead(nn.Module):
         return {"seg_preds": out.permute(0, 3, 1, 2)[:, :self.num_classes]}
 
     def loss(self, example, preds_dicts, **kwargs):
-        raise NotImplementedError("SingleConvHead.loss: segmentation training is out of scope (SegLoss is not built)")
+        """{'seg_loss': [weight * SegLoss(seg_preds, voxel_labels - 1)]} (seg_head.py:86-96); ``example['voxel_labels']``: (B,1,H,W)
+        integer, 0 = unlabelled, on the device"""
+        if self.loss_func is None:
+            raise ValueError("SingleConvHead.loss: the head was built without a loss")
+        seg_preds = preds_dicts["seg_preds"]
+        seg_labels = get_labels(example["voxel_labels"].squeeze(1), tuple(seg_preds.shape[2:]))
+        return {"seg_loss": [self.weight * self.loss_func(seg_preds, seg_labels)]}
 
     @torch.no_grad()
     def predict(self, example, preds_dicts, test_cfg, **kwargs):

@@ -54,6 +54,16 @@ def one_cycle(step: int, total_step: int, lr_max: float, moms: Sequence[float], 
 _SideStream = ops.SideStream
 
 
+def seg_loss_scale_value(seg_loss_decay) -> float:
+    """the trainer's ``seg_loss_decay`` (trainer.py:116-126) as the host factor of the seg loss.  Only the static, non-negative mode is
+    built: the dynamic mode (a negative value: the factor follows the ratio of the two losses) needs the losses on the host."""
+    v = float(seg_loss_decay)
+    if not v >= 0.0:
+        raise ValueError(f"seg_loss_scale must be a non-negative float (got {seg_loss_decay}); the trainer's dynamic mode (negative "
+                         "seg_loss_decay, trainer.py:116-126) needs a readback of the losses and is not built")
+    return v
+
+
 class ParamStore:
     """All trainable parameters of a module in ONE flat fp32 buffer (+ flat grad / Adam moments);
     every parameter starts on a 16-byte boundary.  The flat gradient buffer is what gets all-reduced
@@ -439,6 +449,17 @@ class PolarPillarTrainStep:
         last_blk = len(neck.blocks) - 1
         first_last = min((ps.offsets[n][0] for n in ps.names if order_key(n) >= 1 + 2 * last_blk), default=first_head)
         self.buckets = [b for b in ((first_head, ps.total), (first_last, first_head), (0, first_last)) if b[1] > b[0]]
+        # ---- seg super-task (point_pillars.py:99-103): the head's parameters sort between the RPN and the bbox head (order_key 999), i.e. into
+        # the second gradient bucket
+        self.seg = self.seg_loss = None
+        seg_head = getattr(model, "seg_head", None)
+        if seg_head is not None:
+            from .seg_heads import SegHeadTrain
+            if seg_head.loss_func is None:
+                raise ValueError("training step: the seg head was built without a loss")
+            self.seg = SegHeadTrain(seg_head, ps.p["seg_head.conv.weight"], ps.p["seg_head.conv.bias"], ps.g["seg_head.conv.weight"],
+                                    ps.g["seg_head.conv.bias"], side=ps.side)
+        self._seg_labels = None
         self.sched = dict(total=total_steps, lr_max=lr_max, moms=tuple(moms), div=div_factor, pct=pct_start)
         self.wd, self.max_norm, self.beta2, self.eps = weight_decay, max_norm, beta2, eps
         self.iter = 0
@@ -555,6 +576,10 @@ class PolarPillarTrainStep:
                 off += self.up_filters[j]
         self._packs_ready(1)    # models with a single block reach the head without having met event 1 in the loop
         self.x2 = out
+        self.seg_logits = None
+        if self._seg_labels is not None:
+            # the pillar-features first layer builds no dense canvas: the canvas part of the logits is computed on the pillar rows
+            self.seg_logits = self.seg.forward(canvas, out, vi=self.vi if isinstance(first, _PillarConv) else None)
         # ---- head
         mul = add = None
         if self.has_pos:
@@ -619,7 +644,7 @@ class PolarPillarTrainStep:
         return [(p, n, tg) for p, n, tg in zip(self.preds_tasks, self.task_ncls, targets)]
 
     # ------------------------------------------------------------------------------------------
-    def _backward(self, targets: ops.CenterLossTargets, loss_out, grad_scale: float):
+    def _backward(self, targets: ops.CenterLossTargets, loss_out, grad_scale: float, seg_dlogits=None):
         ps = self.ps
         tasks = self._task_list(targets)
         loss_out = loss_out if isinstance(loss_out, (list, tuple)) else [loss_out]
@@ -684,6 +709,10 @@ class PolarPillarTrainStep:
                 dmid = c1.bwd(d)
                 dmid = ops.tanh_bwd(self.cal_mid[kind], dmid, dx=dmid)
                 c0.bwd(dmid, need_dx=False)
+        if seg_dlogits is not None:
+            # seg head: its RPN half joins d_x2 before the RPN's backward starts; all its parameter gradients (second bucket) are queued here
+            self.seg.backward_x2(seg_dlogits, d_x2)
+            self.seg.backward_x1(seg_dlogits, need_dx=False)
         self._bucket_ready(0)   # every head gradient is queued: its exchange overlaps the backward of the RPN
         # RPN
         nblk = len(self.blocks)
@@ -704,6 +733,8 @@ class PolarPillarTrainStep:
                 self._bucket_ready(1)
         r = self.reader
         sparse = isinstance(self.blocks[0][0].conv, _PillarConv)      # then d_block is d(pillar features) (n_cap, C), not a canvas gradient
+        if seg_dlogits is not None:
+            self.seg.backward_canvas(seg_dlogits, d_block)      # the seg head's canvas half: d_canvas, or d_features at the pillar rows
         ops.dynamic_pfn_bwd(self.points, self.vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset,
                             d_features=d_block if sparse else None, d_canvas=None if sparse else d_block, dw0=ps.g[self.w0], dw1=ps.g[self.w1])
         ps.side.join()
@@ -754,8 +785,27 @@ class PolarPillarTrainStep:
         if getattr(self, "_pack_events", None) is not None:
             torch.cuda.current_stream().wait_event(self._pack_events[k])
 
-    def forward_backward(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, grad_scale=1.0):
-        """forward + loss + backward; gradients land in ``self.ps.flat_g`` (overwritten, not accumulated)"""
+    def forward_backward(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, grad_scale=1.0, voxel_labels=None,
+                         seg_loss_scale=1.0):
+        """forward + loss + backward; gradients land in ``self.ps.flat_g`` (overwritten, not accumulated).
+
+        ``voxel_labels`` (B,1,H,W) integer on the device, 0 = unlabelled (the dataset's majority vote, preprocess.py:172-191): the seg
+        super-task trains jointly -- the total loss is det_loss + seg_head.weight * seg_loss_scale * SegLoss; the returned vector is the
+        det loss as before and ``self.seg_loss`` the device vector [loss, lovasz, ce, n_valid, n_present] of the unweighted SegLoss.
+        ``seg_loss_scale``: the trainer's seg_loss_decay as a non-negative host float.  None (or a model without a seg head): the
+        det-only step; a seg head's gradients are then zero."""
+        seg_scale = seg_loss_scale_value(seg_loss_scale)
+        self._seg_labels = self.seg_loss = None
+        if voxel_labels is not None:
+            if self.seg is None:
+                raise ValueError("voxel_labels given, but the model has no seg head")
+            from .seg_heads import get_labels
+            hip.require_device(voxel_labels)
+            assert voxel_labels.dim() == 4 and voxel_labels.shape[1] == 1, "voxel_labels must be (B, 1, H, W)"
+            self._seg_labels = get_labels(voxel_labels.squeeze(1), (self.spec.grid[1], self.spec.grid[0]))
+        elif self.seg is not None:
+            self.seg.gw.zero_()
+            self.seg.gb.zero_()
         if getattr(self, "_iter_start", None) is None and self.dev.type == "cuda":
             self._iter_start = torch.cuda.Event()
         if getattr(self, "_iter_start", None) is not None:
@@ -767,12 +817,21 @@ class PolarPillarTrainStep:
             for preds, ncls, tg in self._task_list(targets):
                 order, boxes = self._loss_sources(preds)
                 losses.append(ops.center_loss(preds["hm"], ncls, boxes, tg, self.code_weights, self.loss_weight, with_vel="vel" in preds))
+            seg_dlogits = None
+            if self._seg_labels is not None:
+                head = self.seg.head
+                # labels exist only on cells that hold labelled points (preprocess.py:172-191), so the point count bounds the valid cells: the
+                # sort's launches are sized by it, not by the map.  More labelled cells than points: the loss vector is NaN (pn_seg_loss_f32)
+                self.seg_loss, seg_dlogits = head.loss_func.loss_and_grad(ops.as_nchw(self.seg_logits)[:, :head.num_classes], self._seg_labels,
+                                                                          scale=float(head.weight) * seg_scale * grad_scale,
+                                                                          max_valid=max(int(self.vi.n_cap), 1))
             self._packs_ready(2)
-            self._backward(targets, losses, grad_scale)
+            self._backward(targets, losses, grad_scale, seg_dlogits)
             loss = losses[0] if len(losses) == 1 else torch.stack(losses)      # several tasks: one row per task (the trainer sums the det_loss terms)
         finally:
             self.ps.fresh = None
             self._pack_events = None
+            self._seg_labels = None
         return loss
 
     def optimizer_step(self):
@@ -798,7 +857,7 @@ class PolarPillarTrainStep:
     def invalidate_inference_plans(self):
         invalidate_inference_plans(self.model)
 
-    def step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None):
+    def step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0):
         import torch.distributed as dist
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if multi and self.ps.side.on and dist.get_backend() == "gloo":
@@ -806,9 +865,9 @@ class PolarPillarTrainStep:
             # extra streams the device's hardware queues are oversubscribed across processes and every collective waits for a time slice
             # (1585 against 42 ms per iteration, two ranks on one GPU) -- one stream per rank there
             self.ps.side.on = False
-        return self._step(points, sample_offsets, batch, targets, grid_ind)
+        return self._step(points, sample_offsets, batch, targets, grid_ind, voxel_labels, seg_loss_scale)
 
-    def _step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None):
+    def _step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0):
         import torch.distributed as dist
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         from .dist_utils import GradExchange
@@ -826,7 +885,8 @@ class PolarPillarTrainStep:
             self._bufsync.sync(force=force)
         # the reference averages the gradients over ranks (dist_utils.py:17-28): fold 1/world into the loss gradient
         try:
-            loss = self.forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world)
+            loss = self.forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world, voxel_labels=voxel_labels,
+                                         seg_loss_scale=seg_loss_scale)
             if self._exchange is not None:
                 self._exchange.finish()   # the last bucket (reader + first blocks), then the stream waits for all of them
         finally:
