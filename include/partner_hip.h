@@ -854,6 +854,34 @@ int pn_seg_loss_f32(const float *logits, int pixel_stride, long long cells, int 
                     int labels_int64, long long ignore, long long max_valid, float scale, float *out,
                     int32_t *status, float *dlogits, void *workspace, size_t workspace_bytes,
                     pn_stream_t stream);
+/* The seg super-task's targets, built on the device (csrc/seg_labels.hip).
+ *
+ * pn_voxel_labels_vote: Voxelization.get_grid_ind (det3d/datasets/pipelines/voxelization.py:40-60) + AssignLabel.assign_voxel_labels
+ * (det3d/datasets/pipelines/preprocess.py:170-191): per occupied cell the label most of its points carry.
+ *   point_labels  DEVICE, n_labels entries in the order of the points the index was built from; label_dtype 0 = uint8, 1 = int32,
+ *                 2 = int64
+ *   voxel_start / order / unq_keys / num_voxels  the VoxelIndex of pn_unique_rank_bitmap + pn_bucket_points (the points of voxel v are
+ *                 order[voxel_start[v] .. voxel_start[v + 1]), its cell is unq_keys[v]); voxel_capacity = the index's n_capacity
+ *   grid, batch   (R, T, Z) and the sample count: the maps have batch * Z * T * R cells, indexed by the cell key
+ *   voxel_labels  (B, Z, T, R) int64 in the reference's grid_size[::-1] order, 0 where no labelled point falls; may be NULL
+ *   loss_labels   (B * Z * T * R) int32 holding label - 1, and -1 elsewhere: what SegLoss takes (get_labels of equal shapes); may be NULL
+ * A point votes when its label is in [0, 255] and it lies in a voxel run (a point without a cell is in none).  The winner has the
+ * most votes, the lowest label among equals (np.argmax); label 0 votes like any other, so a cell that 0 wins is unlabelled.
+ * Departures: counts do not wrap at 65536 (the reference counts in uint16); a label above 255 does not vote (the reference raises
+ * IndexError).  Two launches (fill + vote) whatever the data, everything bounded by the device-side num_voxels, nothing read back or
+ * allocated, integer arithmetic only: capturable and bit-reproducible.
+ *
+ * pn_pool_labels: the down-sampling branch of get_labels (det3d/models/seg_heads/seg_head.py:33-49).  labels (B, z, h, w) DEVICE
+ * (label_dtype as above; z = 1 for a 2-D map) -> out (B, z / kh, h / kw, w / kl) int64: per window the most frequent label among
+ * 1..255 (0 is excluded, the lowest wins ties: torch.argmax) minus one, -1 for a window without one.  Trailing planes / rows / columns
+ * that do not fill a window are dropped (AvgPool).
+ */
+int pn_voxel_labels_vote(const void *point_labels, int label_dtype, int n_labels, const int32_t *voxel_start,
+                         const int32_t *order, const uint32_t *unq_keys, const int32_t *num_voxels,
+                         int voxel_capacity, const int32_t *grid, int batch, int64_t *voxel_labels,
+                         int32_t *loss_labels, pn_stream_t stream);
+int pn_pool_labels(const void *labels, int label_dtype, int batch, int z, int h, int w, int kh, int kw, int kl,
+                   int64_t *out, pn_stream_t stream);
 /* Panoptic fusion of one sample (SingleConvHead.predict_panoptic, seg_head.py:99-168): pn_seg_point_labels fused with the
  * nearest-box search, one launch writing labels[n] and instance[n] (both int64).  seg_sample: the sample's logits (h, w, classes)
  * with pixel_stride floats between pixels (a padded NHWC buffer is read in place).  points: the sample's first row, point_stride

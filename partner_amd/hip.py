@@ -174,6 +174,8 @@ SIGNATURES = {
     "pn_seg_loss_tile_elems": (_I, [_I]),
     "pn_seg_loss_workspace_bytes": (_SZ, [C.c_longlong, _I, C.c_longlong]),
     "pn_seg_loss_f32": (_I, [_P, _I, C.c_longlong, _I, _P, _I, C.c_longlong, C.c_longlong, _F, _P, _P, _P, _P, _SZ, _P]),
+    "pn_voxel_labels_vote": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "pn_pool_labels": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "pn_panoptic_points_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _F, _P, _I, _P, _P, _P, _I, _P, _F, _P, _P, _P]),
     "pn_panoptic_points_batched_f32": (_I, [_P, C.c_longlong, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _F, _F, _P, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P,
                                             _P]),

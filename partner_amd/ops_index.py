@@ -229,6 +229,50 @@ def scatter_mean(points: torch.Tensor, vi: VoxelIndex, v_cap: Optional[int] = No
     return out
 
 
+_LABEL_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}
+
+
+def voxel_labels_from_points(point_labels: torch.Tensor, vi: VoxelIndex, *, dense: bool = True, loss_labels: bool = False):
+    """The seg super-task's targets from per-point labels (Voxelization.get_grid_ind, voxelization.py:40-60, + AssignLabel.
+    assign_voxel_labels, preprocess.py:170-191): per cell of ``vi`` the label most of its points carry (the lowest among equals), 0 where
+    no labelled point falls.  ``point_labels``: device uint8 / int32 / int64, one per point of the list ``vi`` was built from; labels
+    < 0 and > 255 do not vote.  ``vi``: a ``build_voxel_index`` result (its ``voxel_start`` / ``order`` runs are what is walked).
+    ``dense`` -> voxel_labels (B, Z, T, R) int64; ``loss_labels`` -> (B * Z * T * R,) int32 holding label - 1 and -1 elsewhere (what
+    SegLoss takes).  Both: the pair (voxel_labels, loss_labels).  Two launches, nothing is read back: capturable."""
+    hip.require_device(point_labels)
+    assert vi.order is not None and vi.voxel_start is not None, "voxel_labels_from_points needs the index's voxel runs (voxel_start / order)"
+    assert dense or loss_labels, "no output asked for"
+    if point_labels.dtype not in _LABEL_DTYPES:
+        raise TypeError(f"point_labels must be uint8, int32 or int64 (got {point_labels.dtype})")
+    point_labels = point_labels.reshape(-1).contiguous()
+    assert point_labels.shape[0] == vi.n_cap, "one label per point of the list the index was built from"
+    dev = point_labels.device
+    r, t, z = vi.spec.grid
+    out_dense = torch.empty((vi.batch, z, t, r), dtype=torch.int64, device=dev) if dense else None
+    out_loss = torch.empty((vi.num_cells,), dtype=torch.int32, device=dev) if loss_labels else None
+    _, _, g = vi.spec.c_arrays()
+    hip.call("pn_voxel_labels_vote", point_labels.data_ptr(), _LABEL_DTYPES[point_labels.dtype], vi.n_cap, vi.voxel_start.data_ptr(),
+             vi.order.data_ptr(), vi.unq_keys_ptr, vi.num_voxels.data_ptr(), vi.n_cap, g, vi.batch, hip.ptr(out_dense), hip.ptr(out_loss),
+             hip.stream())
+    if dense and loss_labels:
+        return out_dense, out_loss
+    return out_dense if dense else out_loss
+
+
+def pool_labels(labels: torch.Tensor, kh: int, kw: int, kl: int) -> torch.Tensor:
+    """labels (B, Z, H, W) device uint8 / int32 / int64 -> (B, Z // kh, H // kw, W // kl) int64: per window the most frequent label among
+    1..255 minus one (the lowest wins ties), -1 for a window without one (seg_head.py:33-49)"""
+    hip.require_device(labels)
+    if labels.dtype not in _LABEL_DTYPES:
+        raise TypeError(f"labels must be uint8, int32 or int64 (got {labels.dtype})")
+    assert labels.dim() == 4
+    labels = labels.contiguous()
+    b, z, h, w = labels.shape
+    out = torch.empty((b, z // kh, h // kw, w // kl), dtype=torch.int64, device=labels.device)
+    hip.call("pn_pool_labels", labels.data_ptr(), _LABEL_DTYPES[labels.dtype], b, z, h, w, int(kh), int(kw), int(kl), out.data_ptr(), hip.stream())
+    return out
+
+
 def hard_voxel_mean(voxels: torch.Tensor, num_points: torch.Tensor) -> torch.Tensor:
     hip.require_device(voxels, num_points)
     voxels = voxels.contiguous()

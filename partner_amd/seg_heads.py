@@ -4,7 +4,8 @@ SegLoss (det3d/models/losses/seg_loss.py:8-22).  Secondary to the detection hot 
 fusion with the detection boxes run on the HIP kernels (eval).  Training: SegLoss = Lovasz softmax + cross entropy with its gradient
 (csrc/seg_loss.hip: device-resident compaction, segmented radix sort, integer scans; nothing is read back), ``SingleConvHead.loss``, and
 ``SegHeadTrain``, the head's explicit forward / backward (1x1 convolutions, the bilinear up-sampling and its adjoint) that
-``train.PolarPillarTrainStep`` drives.  Not built: the pooled down-sampling branch of ``get_labels`` (seg_head.py:33-49)."""
+``train.PolarPillarTrainStep`` drives.  The targets: ``ops.voxel_labels_from_points`` (the dataset's per-cell majority vote) and the
+pooled down-sampling branch of ``get_labels`` (seg_head.py:33-49), both on csrc/seg_labels.hip."""
 from __future__ import annotations
 
 import ctypes as C
@@ -30,13 +31,33 @@ def seg_loss_sizes() -> dict:
     return dict(tile=lib.pn_seg_loss_tile_elems(0), block=lib.pn_seg_loss_tile_elems(1), chunk=lib.pn_seg_loss_tile_elems(2))
 
 
+class PooledLabelsOnHost(hip.PartnerHipError, NotImplementedError):
+    """host labels reached the pooled branch of ``get_labels``: like every operator it has no CPU fallback (PartnerHipError); callers that
+    probed the branch before it existed keep seeing the NotImplementedError it used to raise for them"""
+
+
 def get_labels(labels: torch.Tensor, pred_shape) -> torch.Tensor:
     """semantic labels for the loss from ``voxel_labels`` (0 = unlabelled): equal shapes -> ``labels - 1`` (seg_head.py:30-32; hence the
-    config's ``ignore=-1``).  The pooled down-sampling of labels larger than the prediction (seg_head.py:33-49) is not built."""
-    if tuple(labels.shape[1:]) == tuple(pred_shape):
+    config's ``ignore=-1``).  Labels larger than the prediction (seg_head.py:33-49) are pooled on the device (`pn_pool_labels`): per
+    window of (kh, kw, kl) = floor(label shape / prediction shape) cells -- kh = Z for (B,Z,H,W) labels against a 2-D prediction -- the
+    most frequent label among 1..255 minus one, the lowest among equals, -1 for a window without one; int64, (B, H // kw, W // kl) or
+    (B, Z // kh, H // kw, W // kl) (rows / columns that do not fill a window are dropped, as AvgPool does)."""
+    label_shape, pred_shape = tuple(labels.shape[1:]), tuple(pred_shape)
+    if label_shape == pred_shape:
         return labels - 1
-    raise NotImplementedError(f"get_labels: labels {tuple(labels.shape[1:])} against predictions {tuple(pred_shape)} -- the pooled "
-                              "down-sampling branch of get_labels (seg_head.py:33-49) is not built")
+    if len(label_shape) not in (2, 3) or len(pred_shape) not in (2, 3) or len(pred_shape) > len(label_shape):
+        raise ValueError(f"get_labels: labels {label_shape} against predictions {pred_shape}")
+    kw, kl = label_shape[-2] // pred_shape[-2], label_shape[-1] // pred_shape[-1]
+    kh = 1 if len(label_shape) == 2 else (label_shape[0] if len(pred_shape) == 2 else label_shape[0] // pred_shape[0])
+    if min(kh, kw, kl) < 1:
+        raise ValueError(f"get_labels: labels {label_shape} are smaller than the predictions {pred_shape}")
+    if not labels.is_cuda:
+        raise PooledLabelsOnHost(f"get_labels: labels {label_shape} against predictions {pred_shape} -- the pooled down-sampling branch of "
+                                 "get_labels (seg_head.py:33-49) is built for device tensors only (pn_pool_labels); there is no host path")
+    if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
+        labels = labels.to(torch.int64)
+    out = ops.pool_labels(labels if labels.dim() == 4 else labels.unsqueeze(1), kh, kw, kl)
+    return out.squeeze(1)       # a single plane is dropped, as the reference's squeeze(-3) does
 
 
 def seg_loss_nhwc(logits: torch.Tensor, pixel_stride: int, num_classes: int, labels: torch.Tensor, ignore: int, scale: float = 1.0,

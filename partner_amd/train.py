@@ -459,7 +459,7 @@ class PolarPillarTrainStep:
                 raise ValueError("training step: the seg head was built without a loss")
             self.seg = SegHeadTrain(seg_head, ps.p["seg_head.conv.weight"], ps.p["seg_head.conv.bias"], ps.g["seg_head.conv.weight"],
                                     ps.g["seg_head.conv.bias"], side=ps.side)
-        self._seg_labels = None
+        self._seg_labels = self._point_labels = None
         self.sched = dict(total=total_steps, lr_max=lr_max, moms=tuple(moms), div=div_factor, pct=pct_start)
         self.wd, self.max_norm, self.beta2, self.eps = weight_decay, max_norm, beta2, eps
         self.iter = 0
@@ -547,6 +547,11 @@ class PolarPillarTrainStep:
             keys = ops.keys_from_grid_ind(grid_ind.to(torch.int64).contiguous(), spec, batch)
             n_dev = None
         self.vi = ops.build_voxel_index(keys, spec, batch, n_dev=n_dev, want_unq=False, sorted_runs=True)
+        if self._point_labels is not None:
+            # the seg targets from the iteration's own index: per cell the majority of its points' labels, as the loss's int32 label - 1
+            # (-1 = ignore) -- no int64 voxel_labels map, no get_labels pass
+            self._seg_labels = ops.voxel_labels_from_points(self._point_labels, self.vi, dense=False, loss_labels=True).view(
+                batch, spec.grid[1], spec.grid[0])
         self.points = points
         canvas = torch.empty((batch, spec.grid[1], spec.grid[0], self.reader.out_channels), dtype=torch.float32, device=self.dev)
         first = self.blocks[0][0].conv
@@ -786,17 +791,30 @@ class PolarPillarTrainStep:
             torch.cuda.current_stream().wait_event(self._pack_events[k])
 
     def forward_backward(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, grad_scale=1.0, voxel_labels=None,
-                         seg_loss_scale=1.0):
+                         seg_loss_scale=1.0, point_labels=None):
         """forward + loss + backward; gradients land in ``self.ps.flat_g`` (overwritten, not accumulated).
 
         ``voxel_labels`` (B,1,H,W) integer on the device, 0 = unlabelled (the dataset's majority vote, preprocess.py:172-191): the seg
         super-task trains jointly -- the total loss is det_loss + seg_head.weight * seg_loss_scale * SegLoss; the returned vector is the
         det loss as before and ``self.seg_loss`` the device vector [loss, lovasz, ce, n_valid, n_present] of the unweighted SegLoss.
-        ``seg_loss_scale``: the trainer's seg_loss_decay as a non-negative host float.  None (or a model without a seg head): the
+        ``seg_loss_scale``: the trainer's seg_loss_decay as a non-negative host float.
+        ``point_labels`` (one device uint8 / int32 / int64 label per row of ``points``; < 0: unlabelled) instead of ``voxel_labels``: the
+        step builds the targets itself from its voxel index (``ops.voxel_labels_from_points``: the dataset's majority vote on the device) and
+        trains exactly as with the ``voxel_labels`` that vote gives.  Both: ValueError.  Neither (or a model without a seg head): the
         det-only step; a seg head's gradients are then zero."""
         seg_scale = seg_loss_scale_value(seg_loss_scale)
-        self._seg_labels = self.seg_loss = None
-        if voxel_labels is not None:
+        self._seg_labels = self._point_labels = self.seg_loss = None
+        if voxel_labels is not None and point_labels is not None:
+            raise ValueError("give voxel_labels or point_labels, not both")
+        if point_labels is not None:
+            if self.seg is None:
+                raise ValueError("point_labels given, but the model has no seg head")
+            hip.require_device(point_labels)
+            if self.spec.grid[2] != 1:
+                raise ValueError("point_labels: the seg head's map is 2-D, the grid must have one cell along z")
+            assert point_labels.numel() == points.shape[0], "point_labels must hold one label per row of points"
+            self._point_labels = point_labels
+        elif voxel_labels is not None:
             if self.seg is None:
                 raise ValueError("voxel_labels given, but the model has no seg head")
             from .seg_heads import get_labels
@@ -831,7 +849,7 @@ class PolarPillarTrainStep:
         finally:
             self.ps.fresh = None
             self._pack_events = None
-            self._seg_labels = None
+            self._seg_labels = self._point_labels = None
         return loss
 
     def optimizer_step(self):
@@ -857,7 +875,8 @@ class PolarPillarTrainStep:
     def invalidate_inference_plans(self):
         invalidate_inference_plans(self.model)
 
-    def step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0):
+    def step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0,
+             point_labels=None):
         import torch.distributed as dist
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if multi and self.ps.side.on and dist.get_backend() == "gloo":
@@ -865,9 +884,10 @@ class PolarPillarTrainStep:
             # extra streams the device's hardware queues are oversubscribed across processes and every collective waits for a time slice
             # (1585 against 42 ms per iteration, two ranks on one GPU) -- one stream per rank there
             self.ps.side.on = False
-        return self._step(points, sample_offsets, batch, targets, grid_ind, voxel_labels, seg_loss_scale)
+        return self._step(points, sample_offsets, batch, targets, grid_ind, voxel_labels, seg_loss_scale, point_labels)
 
-    def _step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0):
+    def _step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0,
+              point_labels=None):
         import torch.distributed as dist
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         from .dist_utils import GradExchange
@@ -886,7 +906,7 @@ class PolarPillarTrainStep:
         # the reference averages the gradients over ranks (dist_utils.py:17-28): fold 1/world into the loss gradient
         try:
             loss = self.forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world, voxel_labels=voxel_labels,
-                                         seg_loss_scale=seg_loss_scale)
+                                         seg_loss_scale=seg_loss_scale, point_labels=point_labels)
             if self._exchange is not None:
                 self._exchange.finish()   # the last bucket (reader + first blocks), then the stream waits for all of them
         finally:
