@@ -912,6 +912,36 @@ int pn_panoptic_points_batched_f32(const float *seg, long long sample_stride, in
                                    const int64_t *box_labels, const int64_t *instances, const int32_t *count,
                                    const int32_t *sem2box, float score_thr, int64_t *labels, int64_t *instance,
                                    pn_stream_t stream);
+/* pn_panoptic_points_batched_f32 for ALL nsectors * batch stacked (sector-major) samples of a sweep in one launch
+ * (SingleConvHead.predict_panoptic_sweep; PolarStreamBDCP, polarstream.py:423-460, where every sector's logits exist before the
+ * first NMS and every sector's detection list is a buffer of its own).  Stacked sample k = s * batch + b: logits at
+ * seg + k * sample_stride, point rows [offsets[k], offsets[k + 1]) (offsets: DEVICE int32[nsectors * batch + 1]) of the flat
+ * grid_ind / points arrays, boxes = row b of jobs[s]'s (batch, cap, .) list, rotation jobs[s].cos_a / sin_a.  jobs: HOST array of
+ * nsectors (<= 32) entries, copied into the kernel's arguments: nothing is uploaded, the call can be captured.  Per point the
+ * arithmetic of pn_panoptic_points_batched_f32; the outputs are bit-identical to nsectors calls of it on (seg + s * batch *
+ * sample_stride, offsets + s * batch, jobs[s]).  The box count is clamped to cap.  jobs == NULL: labels only (points, sem2box and
+ * instance may then be NULL).
+ * dest == NULL: row r writes labels[r] / instance[r] (stacked order).  dest != NULL (DEVICE int64[n_total], the flat
+ * key_points_index; needs out_offsets: DEVICE int32[batch + 1]): DATASET order -- the row of sample b goes to slot
+ * out_offsets[b] + dest[r] of labels / instance, each out_total entries long, which the call zero-fills on the stream first
+ * (single_stage.py:118-128).  A row whose dest lies outside [0, out_offsets[b + 1] - out_offsets[b]), or whose slot lies outside
+ * [0, out_total), is dropped.  Rows of a sample sharing a dest: one of them wins, which is unspecified.
+ * PN_ERR_INVALID without a launch: null pointers, cap < 1, box_stride < 2, point_stride < x_col + 2, dest without out_offsets,
+ * more than 32 sectors or 65535 stacked samples. */
+typedef struct {
+  const float *boxes;
+  const float *scores;
+  const int64_t *label_preds;
+  const int64_t *instances;
+  const int32_t *count;
+  int32_t box_stride, cap;
+  float cos_a, sin_a;
+} pn_panoptic_sector_job;
+int pn_panoptic_points_sweep_f32(const float *seg, long long sample_stride, int nsectors, int batch, int h, int w, int classes,
+                                 int pixel_stride, const int64_t *grid_ind, const int32_t *offsets, int n_total,
+                                 const float *points, int point_stride, int x_col, const pn_panoptic_sector_job *jobs,
+                                 const int32_t *sem2box, float score_thr, const int64_t *dest, const int32_t *out_offsets,
+                                 long long out_total, int64_t *labels, int64_t *instance, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * next-1  sparse 3-D convolutions of the middle encoder SpMiddleResNetFHD

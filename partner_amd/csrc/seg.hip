@@ -246,6 +246,105 @@ __global__ __launch_bounds__(kPanopticBlock) void panoptic_points_batched_kernel
   if (i < n) a.instance[row] = best_row >= 0 ? instances[best_row] : 0;
 }
 
+// The panoptic fusion of a whole SWEEP in one launch (SingleConvHead.predict_panoptic_sweep; PolarStreamBDCP has every sector's logits
+// before its first NMS runs, and every sector's detection list is a buffer of its own, so the per-point work does not depend on the
+// sector loop).  blockIdx.y = k = s * bs + b, the stacked (sector-major) sample: logits seg + k * sample_stride, point rows
+// [offsets[k], offsets[k + 1]), the boxes of row b of sector s's list and sector s's rotation -- the job table travels in the kernel
+// arguments, nothing is uploaded.  Per lane the code of panoptic_points_batched_kernel, statement for statement: sector s of this launch
+// and the batched launch on (seg + s * bs * sample_stride, offsets + s * bs, sector s's list) write the same bits.
+// dest != NULL: dataset order -- row `row` of sample b goes to out[out_offsets[b] + dest[row]] (single_stage.py:118-128, the
+// key_points_index scatter), dropped when dest[row] lies outside [0, out_offsets[b + 1] - out_offsets[b]) or the slot outside
+// [0, out_total); the entry zero-fills the outputs first.
+constexpr int kMaxSweepSectors = 32;
+struct SweepJob {
+  const float* boxes; const float* scores; const int64_t* box_labels; const int64_t* instances; const int32_t* count;
+  int box_stride, cap; float cos_a, sin_a;
+};
+struct PanopticSweep {
+  const float* seg; long long sample_stride; int bs, H, W, C, pixel_stride;
+  const int64_t* grid_ind; const int32_t* offsets; int n_total;
+  const float* points; int point_stride, x_col;
+  const int32_t* sem2box; float score_thr;
+  const int64_t* dest; const int32_t* out_offsets; long long out_total;
+  int64_t* labels; int64_t* instance;
+  SweepJob job[kMaxSweepSectors];
+};
+
+template <bool kBoxes>
+__global__ __launch_bounds__(kPanopticBlock) void panoptic_points_sweep_kernel(PanopticSweep a) {
+  __shared__ float4 sbox[kBoxes ? kPanopticChunk : 1];
+  const int k = blockIdx.y;
+  const int lo = min(max(a.offsets[k], 0), a.n_total), hi = min(max(a.offsets[k + 1], lo), a.n_total);
+  const int n = hi - lo;
+  if ((int)blockIdx.x * kPanopticBlock >= n) return;      // the whole block: no barrier has been reached
+  const int s = k / a.bs, b = k - s * a.bs;
+  const int i = blockIdx.x * kPanopticBlock + threadIdx.x;
+  const size_t row = (size_t)lo + i;
+  size_t at = row;          // where this lane's outputs go
+  bool keep = i < n;
+  if (keep && a.dest) {
+    const long long o0 = a.out_offsets[b], o1 = a.out_offsets[b + 1];
+    const long long d = a.dest[row], p = o0 + d;
+    keep = d >= 0 && d < o1 - o0 && p >= 0 && p < a.out_total;
+    at = (size_t)p;
+  }
+  const float cos_a = kBoxes ? a.job[s].cos_a : 1.f, sin_a = kBoxes ? a.job[s].sin_a : 0.f;
+  int want = -1;
+  float px = 0.f, py = 0.f;
+  if (i < n) {
+    const int64_t y = a.grid_ind[row * 3 + 1], x = a.grid_ind[row * 3 + 2];
+    int lab = 0;
+    if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
+      const float* p = a.seg + (size_t)k * a.sample_stride + ((size_t)y * a.W + x) * a.pixel_stride;
+      float top = p[0];
+      int arg = 0;
+      for (int c = 1; c < a.C; ++c)
+        if (p[c] > top) { top = p[c]; arg = c; }
+      lab = arg + 1;
+      if (kBoxes) want = a.sem2box[lab];
+    }
+    if (keep) a.labels[at] = lab;
+    if (kBoxes && want >= 0) {
+      const float* q = a.points + row * a.point_stride + a.x_col;
+      const float qx = q[0], qy = q[1];
+      px = qx * cos_a - qy * sin_a;
+      py = qx * sin_a + qy * cos_a;
+    }
+  }
+  if (!kBoxes) return;
+  const SweepJob& job = a.job[s];
+  const int cap = job.cap, box_stride = job.box_stride;
+  const int m = min(max(job.count[b], 0), cap);
+  const float* boxes = job.boxes + (size_t)b * cap * box_stride;
+  const float* scores = job.scores + (size_t)b * cap;
+  const int64_t* box_labels = job.box_labels + (size_t)b * cap;
+  const int64_t* instances = job.instances + (size_t)b * cap;
+  float best = 0.f;
+  int best_row = -1;
+  for (int c0 = 0; c0 < m; c0 += kPanopticChunk) {
+    const int cnt = min(kPanopticChunk, m - c0);
+    if (c0) __syncthreads();      // every lane is done with the previous chunk
+    for (int j = threadIdx.x; j < cnt; j += kPanopticBlock) {
+      const size_t r = (size_t)(c0 + j);
+      const int64_t bl = box_labels[r];
+      const int lab = (scores[r] > a.score_thr && bl >= 0 && bl <= 0x7fffffff) ? (int)bl : -1;
+      sbox[j] = make_float4(boxes[r * box_stride], boxes[r * box_stride + 1], __int_as_float(lab), 0.f);
+    }
+    __syncthreads();
+    if (want >= 0) {
+      for (int j = 0; j < cnt; ++j) {
+        const float4 e = sbox[j];
+        if (__float_as_int(e.z) == want) {
+          const float dx = px - e.x, dy = py - e.y;
+          const float d = dx * dx + dy * dy;
+          if (best_row < 0 || d < best) { best = d; best_row = c0 + j; }
+        }
+      }
+    }
+  }
+  if (keep) a.instance[at] = best_row >= 0 ? instances[best_row] : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -318,6 +417,46 @@ int pn_panoptic_points_batched_f32(const float* seg, long long sample_stride, in
   a.sem2box = sem2box; a.score_thr = score_thr; a.instance = instance;
   hipLaunchKernelGGL(panoptic_points_batched_kernel<true>, grid, dim3(kPanopticBlock), 0, pn::S(stream), a);
   return pn::check_launch("panoptic_points_batched_kernel");
+}
+
+int pn_panoptic_points_sweep_f32(const float* seg, long long sample_stride, int nsectors, int batch, int h, int w, int classes, int pixel_stride,
+                                 const int64_t* grid_ind, const int32_t* offsets, int n_total, const float* points, int point_stride, int x_col,
+                                 const pn_panoptic_sector_job* jobs, const int32_t* sem2box, float score_thr, const int64_t* dest,
+                                 const int32_t* out_offsets, long long out_total, int64_t* labels, int64_t* instance, pn_stream_t stream) {
+  PN_REQUIRE(nsectors >= 1 && nsectors <= kMaxSweepSectors && batch >= 1 && (long long)nsectors * batch <= 65535,
+             "panoptic_points_sweep: 1..32 sectors, at most 65535 stacked samples");
+  PN_REQUIRE(h >= 1 && w >= 1 && classes >= 1 && pixel_stride >= classes && n_total >= 0 && sample_stride >= 0 && out_total >= 0,
+             "panoptic_points_sweep: bad arguments");
+  PN_REQUIRE(seg && offsets && labels && (grid_ind || n_total == 0), "panoptic_points_sweep: null pointer");
+  PN_REQUIRE(!dest || out_offsets, "panoptic_points_sweep: dest (dataset order) needs out_offsets");
+  PanopticSweep a{};
+  a.seg = seg; a.sample_stride = sample_stride; a.bs = batch; a.H = h; a.W = w; a.C = classes; a.pixel_stride = pixel_stride;
+  a.grid_ind = grid_ind; a.offsets = offsets; a.n_total = n_total; a.labels = labels;
+  a.dest = dest; a.out_offsets = dest ? out_offsets : nullptr; a.out_total = out_total;
+  if (jobs) {
+    PN_REQUIRE((points || n_total == 0) && sem2box && instance, "panoptic_points_sweep: null pointer");
+    PN_REQUIRE(x_col >= 0 && point_stride >= x_col + 2, "panoptic_points_sweep: the point rows must hold columns x_col and x_col + 1");
+    for (int s = 0; s < nsectors; ++s) {
+      const pn_panoptic_sector_job& j = jobs[s];
+      PN_REQUIRE(j.boxes && j.scores && j.label_preds && j.instances && j.count, "panoptic_points_sweep: null pointer in sector %d's list", s);
+      PN_REQUIRE(j.cap >= 1 && j.box_stride >= 2, "panoptic_points_sweep: sector %d: cap < 1 or box_stride < 2", s);
+      a.job[s] = SweepJob{j.boxes, j.scores, j.label_preds, j.instances, j.count, j.box_stride, j.cap, j.cos_a, j.sin_a};
+    }
+    a.points = points; a.point_stride = point_stride; a.x_col = x_col; a.sem2box = sem2box; a.score_thr = score_thr; a.instance = instance;
+  }
+  if (dest) {      // slots no row is sent to read 0, as the reference's new_zeros (single_stage.py:121)
+    int rc = pn::zero_async(labels, (size_t)out_total * sizeof(int64_t), pn::S(stream));
+    if (rc == PN_OK && jobs) rc = pn::zero_async(instance, (size_t)out_total * sizeof(int64_t), pn::S(stream));
+    if (rc != PN_OK) return rc;
+  }
+  if (n_total == 0) return PN_OK;
+  const dim3 grid(pn::cdiv(n_total, kPanopticBlock), nsectors * batch);
+  if (!jobs) {      // labels only
+    hipLaunchKernelGGL(panoptic_points_sweep_kernel<false>, grid, dim3(kPanopticBlock), 0, pn::S(stream), a);
+    return pn::check_launch("panoptic_points_sweep_kernel<labels>");
+  }
+  hipLaunchKernelGGL(panoptic_points_sweep_kernel<true>, grid, dim3(kPanopticBlock), 0, pn::S(stream), a);
+  return pn::check_launch("panoptic_points_sweep_kernel");
 }
 
 }  // extern "C"

@@ -247,7 +247,8 @@ class PolarStream(PointPillars):
     configs) is supported.  With a segmentation head every sector also yields per-point semantic labels ('seg'), and with
     test_cfg.panoptic per-point instance ids ('ins', polarstream.py:161-171): the boxes' ids are carried from sector to sector like
     the stateful NMS's detections, and the merged detections keep their 'instances' (the reference drops them) so that 'ins' can be
-    mapped back to a box.  ``key_points_index`` reordering of the reference's merge_sectors is not built."""
+    mapped back to a box.  Sector examples that carry ``key_points_index`` (per sample, the positions of the sector's points in the
+    dataset's point list) get 'seg' / 'ins' back in that order (merge_sectors, single_stage.py:97-128)."""
 
     def forward_one_sector(self, example, return_loss=True, **kwargs):
         eval_only(self, "PolarStream")
@@ -322,6 +323,8 @@ class PolarStream(PointPillars):
             r = self.forward_one_sector(ex, return_loss, **kw)
             prev = r.pop("next_context", []) if i < len(example) - 1 else []
             r.pop("next_context", None)
+            if "key_points_index" in ex:          # polarstream.py:99-100
+                r["key_points_index"] = ex["key_points_index"]
             rets.append(r)
         out = self.merge_sectors(rets, len(example[-1]["num_points"]), stateful or panoptic)
         if (stateful or panoptic) and "det" in out:
@@ -335,7 +338,8 @@ class PolarStream(PointPillars):
         return_loss=False)`` returns: per-sample detections cut to their counts with 'metadata' (a carried list: the last sector's,
         with 'instances' under panoptic; otherwise the sectors' lists concatenated, with 'cells'), and per-sample {token: tensor} dicts
         for 'seg' / 'ins', the sectors' rows of a sample concatenated in sector order.  ONE readback, of the counts; the per-point
-        outputs are split by the host ``num_points``.  Index bookkeeping only: runs on whatever device the tensors live on."""
+        outputs are split by the host ``num_points``.  Sector examples that all carry ``key_points_index`` put 'seg' / 'ins' into dataset
+        order, as ``merge_sectors`` does, indexing on the tensors' device.  Index bookkeeping only: runs on whatever device the tensors live on."""
         res = {}
         det = out.get("det")
         fields = ("box3d_lidar", "scores", "label_preds")
@@ -370,7 +374,34 @@ class PolarStream(PointPillars):
                     merged[i].setdefault(token, []).append(flat[start:start + n])
                     start += n
             res[key] = [{token: torch.cat(v) for token, v in m.items()} for m in merged]
+        if ("seg" in res or "ins" in res) and all("key_points_index" in ex for ex in examples):
+            batch = len(examples[0]["num_points"])
+            index = [PolarStream._cat_index([ex["key_points_index"][i] for ex in examples]) for i in range(batch)]
+            for key in ("seg", "ins"):
+                if key in res:
+                    res[key] = PolarStream._to_dataset_order(res[key], index)
+            res["key_points_index"] = index      # merge_sectors returns it too (single_stage.py:97-104)
         return res
+
+    @staticmethod
+    def _cat_index(parts):
+        """one sample's ``key_points_index`` pieces (numpy arrays, lists or tensors), sector by sector -> one int64 tensor, on the device
+        the pieces live on (nothing is read back)"""
+        return torch.cat([torch.as_tensor(p).reshape(-1).to(torch.int64) for p in parts])
+
+    @staticmethod
+    def _to_dataset_order(per_sample, index):
+        """single_stage.py:118-128: per sample and token, ``out = zeros_like(v); out[index] = v`` -- the sectors' rows back at their
+        positions in the dataset's point list; positions no row names read 0"""
+        out = []
+        for m, idx in zip(per_sample, index):
+            d = {}
+            for token, v in m.items():
+                tmp = v.new_zeros(v.shape)
+                tmp[idx.to(v.device)] = v
+                d[token] = tmp
+            out.append(d)
+        return out
 
     def _test_flag(self, name) -> bool:
         cfg = self.test_cfg
@@ -382,7 +413,9 @@ class PolarStream(PointPillars):
         """single_stage.py:83-165 for the keys this build produces: losses are lists concatenated over sectors, detections are
         concatenated per sample; with stateful NMS or panoptic fusion (``stateful``) the LAST sector's per-task lists already hold the
         whole sweep (merge_dets :137-153: tasks concatenated, labels offset by the preceding tasks' class counts; 'instances', where the
-        lists carry them, are kept); 'seg' / 'ins' are concatenated per sample and token in sector order (:106-116)"""
+        lists carry them, are kept); 'seg' / 'ins' are concatenated per sample and token in sector order (:106-116); 'key_points_index'
+        (per sector a list of one index array per sample) is concatenated per sample (:97-104), and 'seg' / 'ins' are then scattered to
+        those positions (:118-128)"""
         out = {}
         for k in sectors[0]:
             vals = [s[k] for s in sectors]
@@ -418,6 +451,12 @@ class PolarStream(PointPillars):
                         for token, v in sec[i].items():
                             merged[i].setdefault(token, []).append(v)
                 out[k] = [{token: torch.cat(v) for token, v in m.items()} for m in merged]
+            elif k == "key_points_index":
+                out[k] = [PolarStream._cat_index([sec[i] for sec in vals]) for i in range(batch_size)]
+        if "key_points_index" in out:
+            for k in ("seg", "ins"):
+                if k in out:
+                    out[k] = PolarStream._to_dataset_order(out[k], out["key_points_index"])
         return out
 
 
@@ -427,7 +466,13 @@ class PolarStreamBDCP(PolarStream):
     The previous sweep runs in ``feature_only`` mode (all its sectors stacked in the batch axis, sector-major); the per-layer inputs
     of the neck (RPNBDCP) are glued back into whole-sweep maps and warped into the current sweep's frame by the ego rotation
     (``transform_matrix`` (bs, 2, 2); `pn_polar_warp_f32`).  The current sweep is then streamed sector by sector: trailing-edge context
-    from the sector before, leading-edge context from the warped previous sweep.  Eval mode, detection super-task."""
+    from the sector before, leading-edge context from the warped previous sweep.  Eval mode; the detection super-task and, with a seg
+    head, per-point labels ('seg') and under test_cfg.panoptic per-point instance ids ('ins', polarstream.py:423-460): the detection list
+    is then carried from sector to sector as under stateful NMS and keeps its 'instances'.  All sectors' logits exist before the first
+    NMS, so the device path runs the whole sweep's per-point work as ONE launch after the last NMS (`pn_panoptic_points_sweep_f32`).
+    With more than one sector an example's ``key_points_index`` (per stacked sample, the positions of its points in the dataset's point
+    list) puts 'seg' / 'ins' into dataset order (polarstream.py:453-454, single_stage.py:97-128); with one sector it is not read, as in
+    the reference.  ``valid_grid_ind`` must hold one row per point of the stacked point list."""
 
     def __init__(self, reader, backbone, neck, bbox_head, seg_head=None, part_head=None, train_cfg=None, test_cfg=None, pretrained=None,
                  nsectors=1):
@@ -505,8 +550,9 @@ class PolarStreamBDCP(PolarStream):
         eval_only(self, "PolarStreamBDCP")
         if return_loss:
             raise NotImplementedError("PolarStreamBDCP: training (the two-sweep loss path) is not built")
-        if self._test_flag("panoptic"):
-            raise NotImplementedError("PolarStreamBDCP: test_cfg.panoptic (polarstream.py:423-460) is not built; PolarStream has it")
+        if self._test_flag("panoptic") and self.seg_head is None:
+            raise NotImplementedError("PolarStreamBDCP: test_cfg.panoptic (polarstream.py:423-460) needs a seg head -- the panoptic fusion assigns the "
+                                      "boxes' instance ids to the seg head's per-point labels")
 
     def forward_one_sweep(self, example, mode="feature_only", return_loss=False, **kwargs):
         self._refuse_unbuilt(return_loss)
@@ -522,9 +568,11 @@ class PolarStreamBDCP(PolarStream):
                          **({"seg_preds": preds["seg_preds"][i * bs:(i + 1) * bs]} if "seg_preds" in preds else {})}
         if kwargs.get("raw_preds", False) or self.test_cfg is None:
             return [cut(i) for i in range(nsec)]
-        stateful = bool(self._get("stateful_nms", False))
+        stateful, panoptic = bool(self._get("stateful_nms", False)), self._test_flag("panoptic")
         rets, prev_dets = [], None
         metas = example.get("metadata", [None] * batch)
+        key_index = self._key_index_lists(example) if (self.seg_head is not None and nsec > 1) else None
+        cum = 0
         for i in range(nsec):
             pr = cut(i)
             ex = dict(metadata=metas[i * bs:(i + 1) * bs])
@@ -532,12 +580,59 @@ class PolarStreamBDCP(PolarStream):
                 ex["pc_range"] = example["pc_range"][i * bs:(i + 1) * bs]
             det = self.bbox_head.predict(ex, pr, self.test_cfg, sec_id=i, prev_dets=prev_dets)
             rets.append({"det": det})
-            prev_dets = det if stateful and i < nsec - 1 else None
+            prev_dets = det if (stateful or panoptic) and i < nsec - 1 else None      # polarstream.py:444-448
             if self.seg_head is not None:           # polarstream.py:449-463
                 for k in ("num_points", "valid_grid_ind"):
                     ex[k] = example[k][i * bs:(i + 1) * bs]
-                rets[i]["seg"] = self.seg_head.predict(ex, pr, self.test_cfg)
+                if key_index is not None:           # :453-454 (one sector: not read)
+                    rets[i]["key_points_index"] = key_index[i * bs:(i + 1) * bs]
+                if panoptic:                        # :455-460: the sector's slice of the stacked point list, one row per valid_grid_ind row
+                    n = sum(int(v) for v in ex["num_points"])
+                    ex["points"] = example["points"][cum:cum + n]
+                    cum += n
+                    self.seg_head.predict_panoptic(ex, pr, self.test_cfg, rets[i], voxel_shape=self.bbox_head.voxel_shape,
+                                                   class_names=self.bbox_head.class_names, sec_id=i)
+                else:
+                    rets[i]["seg"] = self.seg_head.predict(ex, pr, self.test_cfg)
         return rets
+
+    def _key_index_lists(self, example):
+        """``example['key_points_index']`` as the reference has it, one index array per stacked sample (None without the key); a flat
+        tensor in stacked row order -- the device path's form -- is cut by the host ``num_points``"""
+        kpi = example.get("key_points_index")
+        if kpi is None or not torch.is_tensor(kpi):
+            return kpi
+        return list(torch.split(kpi.reshape(-1), self._host_counts(example)))
+
+    def _key_index_flat(self, example, rows, dev):
+        """the device path's form of ``example['key_points_index']``: ONE (rows,) int64 device tensor in stacked row order.  A device tensor
+        is taken as it is; the reference's per-sample list is concatenated and uploaded once and kept in the example (not capturable)."""
+        kpi = example["key_points_index"]
+        if not (torch.is_tensor(kpi) and kpi.is_cuda):
+            flat = example.get("key_points_index_flat")
+            if flat is None:
+                parts = [kpi] if torch.is_tensor(kpi) else list(kpi)
+                flat = example["key_points_index_flat"] = self._cat_index(parts).to(dev)
+            kpi = flat
+        kpi = kpi.reshape(-1).to(torch.int64).contiguous()
+        assert kpi.shape[0] == rows, "key_points_index must hold one entry per point row"
+        return kpi
+
+    def _sample_offsets(self, example, dev):
+        """(bs + 1,) int32 device offsets of the samples' points in dataset order (a sample's points of all sectors together) and their
+        host values: ``example['sample_offsets']`` when present, otherwise built once from the host ``num_points`` and kept there"""
+        num = self._host_counts(example)
+        bs = len(num) // self.nsectors
+        acc = [0]
+        for b in range(bs):
+            acc.append(acc[-1] + sum(num[b::bs]))
+        offs = example.get("sample_offsets")
+        if offs is None:
+            offs = example["sample_offsets"] = torch.tensor(acc, dtype=torch.int32, device=dev)
+        hip.require_device(offs)
+        assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous() and offs.shape[0] == bs + 1, \
+            "sample_offsets must be a contiguous int32 (bs + 1,) tensor"
+        return offs, acc
 
     def _point_rows(self, example, dev):
         """the stacked sweep's per-point grid indices as ONE (rows, 3) int64 device tensor and the (nsectors * bs + 1,) int32 row offsets
@@ -577,7 +672,10 @@ class PolarStreamBDCP(PolarStream):
         graph.  The previous sweep runs the canvas and the neck up to its last layer's input (no last convolution, no deblocks: nobody
         reads them), and ONE launch warps the border rows the current sweep's streaming pass reads; with one sector the padding is
         circular and the previous sweep is skipped altogether.  The current sweep is the host path's, with the heads' ``device_only`` calls
-        per sector."""
+        per sector.  Under test_cfg.panoptic the list is carried from sector to sector (fresh fixed-capacity buffers of
+        ``nms_post_max_size * (sector + 1)`` rows each), and after the last NMS ONE launch writes every sector's labels and instance ids
+        (``SingleConvHead.predict_panoptic_sweep``); with ``key_points_index`` (more than one sector) that launch -- the labels alone
+        without panoptic -- writes them in dataset order.  ``valid_grid_ind`` must hold one row per point of ``points``."""
         self._refuse_unbuilt(False)
         prev_ex, ex = example
         nsec = self.nsectors
@@ -585,42 +683,73 @@ class PolarStreamBDCP(PolarStream):
         canvas, batch = self._canvas(ex)
         bs = batch // nsec
         preds = self._heads(canvas, self._stream_sectors(canvas, prev_sweep, bs, "eval"))
-        stateful = bool(self._get("stateful_nms", False))
+        stateful, panoptic = bool(self._get("stateful_nms", False)), self._test_flag("panoptic")
+        carry = stateful or panoptic
         metas = ex.get("metadata", [None] * batch)
         dets, segs, prev_dets = [], [], None
+        ordered = self.seg_head is not None and nsec > 1 and ex.get("key_points_index") is not None
+        sweep_launch = panoptic or ordered      # the per-point work of all sectors in one launch after the loop
         if self.seg_head is not None:
             gi, offs = self._point_rows(ex, canvas.device)
             first = [0]
             for v in self._host_counts(ex):
                 first.append(first[-1] + v)
+            if sweep_launch:
+                assert gi.dim() == 2 and gi.shape[1] == 3 and gi.shape[0] == first[-1] <= ex["points"].shape[0], \
+                    "valid_grid_ind must hold one [z, y, x] row per point of the stacked point list"
         for i in range(nsec):
             sec = dict(metadata=metas[i * bs:(i + 1) * bs])
             if "pc_range" in ex:
                 sec["pc_range"] = ex["pc_range"][i * bs:(i + 1) * bs]
             pr = {"det_preds": [{k: v[i * bs:(i + 1) * bs] for k, v in t.items()} for t in preds["det_preds"]]}
-            prev_dets = self.bbox_head.predict(sec, pr, self.test_cfg, sec_id=i, prev_dets=prev_dets if stateful else None, device_only=True)
+            prev_dets = self.bbox_head.predict(sec, pr, self.test_cfg, sec_id=i, prev_dets=prev_dets if carry else None, device_only=True)
             dets.append(prev_dets)
-            if self.seg_head is not None:
+            if self.seg_head is not None and not sweep_launch:
                 # the sector's samples are rows [offs[i * bs], offs[(i + 1) * bs]) of the sweep's flat list: the kernel takes absolute offsets, so
                 # the head gets the whole list with the sector's offsets and writes the sector's rows, which the host counts cut out
                 rows = dict(valid_grid_ind=gi, point_offsets=offs[i * bs:(i + 1) * bs + 1])
                 labels = self.seg_head.predict(rows, {"seg_preds": preds["seg_preds"][i * bs:(i + 1) * bs]}, self.test_cfg, device_only=True)
                 segs.append(labels[first[i * bs]:first[(i + 1) * bs]])
-        out = {"det": dets[-1] if stateful else dets}
-        if self.seg_head is not None:
+        out = {"det": dets[-1] if carry else dets}
+        if sweep_launch:
+            kw = {}
+            if ordered:
+                sample_offs, acc = self._sample_offsets(ex, canvas.device)
+                kw = dict(key_points_index=self._key_index_flat(ex, gi.shape[0], canvas.device), out_offsets=sample_offs, out_total=acc[-1])
+            labels, ins = self.seg_head.predict_panoptic_sweep(preds["seg_preds"], gi, offs, ex["points"], dets if panoptic else None, self.test_cfg,
+                                                               voxel_shape=self.bbox_head.voxel_shape, class_names=self.bbox_head.class_names,
+                                                               nsectors=nsec, **kw)
+            cuts = acc if ordered else [first[i * bs] for i in range(nsec + 1)]      # per sample in dataset order / per sector in stacked order
+            out["seg"] = [labels[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
+            if panoptic:
+                out["ins"] = [ins[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
+            if ordered:
+                out["dataset_order"] = True
+        elif self.seg_head is not None:
             out["seg"] = segs
         return out
 
     def sweep_to_host(self, out, cur_example):
         """The result of ``forward([prev, cur], return_loss=False, device_only=True)`` -> exactly what ``forward([prev, cur],
         return_loss=False)`` returns, with ONE readback (the counts): the stacked example is cut into its sectors' host fields and handed
-        to ``PolarStream.sweep_to_host``; a carried list takes the first sector's metadata, as ``forward`` gives it."""
+        to ``PolarStream.sweep_to_host``; a carried list takes the first sector's metadata, as ``forward`` gives it.  'seg' / 'ins' in dataset
+        order (``out['dataset_order']``: one tensor per sample, written at the ``key_points_index`` positions on the device) only need their
+        token."""
         nsec = self.nsectors
         num = self._host_counts(cur_example)
         bs = len(num) // nsec
         metas = cur_example.get("metadata", [None] * len(num))
         sectors = [dict(num_points=num[i * bs:(i + 1) * bs], metadata=metas[i * bs:(i + 1) * bs]) for i in range(nsec)]
+        per_point = {}
+        if out.get("dataset_order", False):
+            tokens = [m["token"] if isinstance(m, dict) and "token" in m else i for i, m in enumerate(metas[:bs])]
+            per_point = {k: [{tokens[i]: t} for i, t in enumerate(out[k])] for k in ("seg", "ins") if k in out}
+            out = {k: v for k, v in out.items() if k not in ("seg", "ins", "dataset_order")}
         res = PolarStream.sweep_to_host(out, sectors)
+        res.update(per_point)
+        if per_point:
+            lists = self._key_index_lists(cur_example)
+            res["key_points_index"] = [self._cat_index(lists[b::bs]) for b in range(bs)]
         if isinstance(out.get("det"), dict):
             for det, meta in zip(res["det"], metas[:bs]):
                 det["metadata"] = meta
@@ -628,8 +757,10 @@ class PolarStreamBDCP(PolarStream):
 
     def forward(self, example, return_loss=True, **kwargs):
         """example: [previous sweep, current sweep] (polarstream.py:266-290).  ``device_only=True`` (inference): see ``_forward_device``;
-        returns 'det': the last sector's device list under stateful NMS, otherwise the list of per-sector device lists, and with a seg head
-        'seg': the sectors' flat (rows,) int64 label tensors.  ``sweep_to_host`` turns that into what this method returns without the flag."""
+        returns 'det': the last sector's device list under stateful NMS or panoptic (then with 'instances'), otherwise the list of per-sector
+        device lists, and with a seg head 'seg' (under panoptic also 'ins'): the sectors' flat (rows,) int64 tensors -- or, with
+        ``key_points_index`` and more than one sector, one tensor per sample in dataset order, views of one buffer, marked by
+        ``'dataset_order': True``.  ``sweep_to_host`` turns that into what this method returns without the flag."""
         if isinstance(example, dict) or len(example) != 2:
             raise ValueError("PolarStreamBDCP.forward takes a list of two sweeps [previous, current]")
         if kwargs.get("device_only", False) and not return_loss and not kwargs.get("raw_preds", False) and self.test_cfg is not None:
@@ -638,7 +769,7 @@ class PolarStreamBDCP(PolarStream):
         rets = self.forward_one_sweep(example[1], "train" if return_loss else "eval", return_loss, prev_sweep=prev_sweep, **kwargs)
         ex = example[1]
         bs = len(ex["num_points"]) // self.nsectors
-        stateful = self.test_cfg is not None and bool(self._get("stateful_nms", False))
+        stateful = self.test_cfg is not None and (bool(self._get("stateful_nms", False)) or self._test_flag("panoptic"))
         out = self.merge_sectors(rets, bs, stateful)
         if stateful and "det" in out:
             for det, meta in zip(out["det"], ex.get("metadata", [None] * bs)[:bs]):

@@ -42,6 +42,13 @@ class WarpStripJob(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32)]
 
 
+class PanopticSectorJob(C.Structure):
+    """mirror of ``pn_panoptic_sector_job``"""
+
+    _fields_ = [("boxes", C.c_void_p), ("scores", C.c_void_p), ("label_preds", C.c_void_p), ("instances", C.c_void_p), ("count", C.c_void_p),
+                ("box_stride", C.c_int32), ("cap", C.c_int32), ("cos_a", C.c_float), ("sin_a", C.c_float)]
+
+
 class HeadStatJob(C.Structure):
     """mirror of ``pn_head_stat_job``"""
 
@@ -179,6 +186,8 @@ SIGNATURES = {
     "pn_panoptic_points_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _F, _P, _I, _P, _P, _P, _I, _P, _F, _P, _P, _P]),
     "pn_panoptic_points_batched_f32": (_I, [_P, C.c_longlong, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _F, _F, _P, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P,
                                             _P]),
+    "pn_panoptic_points_sweep_f32": (_I, [_P, C.c_longlong, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, C.POINTER(PanopticSectorJob), _P, _F, _P, _P,
+                                          C.c_longlong, _P, _P, _P]),
     "pn_sparse_index_bytes": (_SZ, [_U64]),
     "pn_sparse_index_from_coords": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "pn_sparse_index_downsample": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),

@@ -395,6 +395,88 @@ class SingleConvHead(nn.Module):
                  det["scores"].data_ptr(), det["label_preds"].data_ptr(), det["instances"].data_ptr(), det["count"].data_ptr(), sem2box.data_ptr(),
                  float(score_thr), labels.data_ptr(), ins.data_ptr(), hip.stream())
 
+    @torch.no_grad()
+    def predict_panoptic_sweep(self, seg_preds, grid_ind, offsets, points, dets, test_cfg, *, voxel_shape, class_names, semantic2box=None,
+                               score_thr=0.3, key_points_index=None, out_offsets=None, out_total=None, nsectors=1):
+        """``predict_panoptic(device_only=True)`` for ALL sectors of a sweep in ONE launch (`pn_panoptic_points_sweep_f32`), for a detector
+        that has every sector's logits and detection list at once (PolarStreamBDCP).  ``seg_preds``: the stacked (nsectors * bs, classes,
+        H, W) channels-last logits, sector-major; ``grid_ind`` (rows, 3) int64 / ``offsets`` (nsectors * bs + 1,) int32: the flat rows of
+        ``PolarStreamBDCP._point_rows``; ``points`` (>= rows, F) the stacked point list, one row per ``grid_ind`` row; ``dets``: one
+        device list of ``CenterHead.predict(device_only=True)`` under test_cfg.panoptic per sector (their capacities may differ), or None
+        for the labels alone (``nsectors`` then says how the stacked batch splits, which matters to dataset order only).  Sector s is rotated by ``predict_panoptic``'s angle (``interval * s``; cuboid: ``2 pi / interval * s``),
+        cos / sin taken as ``_launch_batched`` takes them, so the result is bit for bit that of one ``predict_panoptic`` per sector.
+        -> (labels, ins): flat (rows,) int64 in stacked row order; ``ins`` is None without ``dets``.
+
+        ``key_points_index`` (rows,) int64 on the device (the sectors' ``key_points_index`` in stacked row order) with ``out_offsets``
+        (bs + 1,) int32 and ``out_total``: DATASET order (single_stage.py:118-128) -- the row of sample b lands at
+        ``out_offsets[b] + key_points_index[row]`` of (out_total,) outputs, zero-filled first; rows pointing outside their sample are dropped.
+        Nothing is read back and, once the class table is cached, nothing is uploaded."""
+        hip.require_device(seg_preds, grid_ind, offsets)
+        seg = seg_preds
+        assert seg.dim() == 4 and seg.stride(1) == 1, "seg_preds must be the channels-last view produced by forward"
+        total, ncls, h, w = seg.shape
+        dev = seg.device
+        nsec = int(nsectors) if dets is None else len(dets)      # the labels alone: any split of the stacked batch gives the same rows
+        assert nsec >= 1 and total % nsec == 0, "the stacked batch is not a multiple of the number of sectors"
+        bs = total // nsec
+        assert grid_ind.dim() == 2 and grid_ind.shape[1] == 3 and grid_ind.dtype == torch.int64 and grid_ind.is_contiguous(), \
+            "grid_ind must be a contiguous (rows, 3) int64 tensor"
+        assert offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.shape[0] == total + 1, \
+            "offsets must be a contiguous int32 (nsectors * bs + 1,) tensor"
+        assert seg.stride(2) == w * seg.stride(3) and (total == 1 or seg.stride(0) >= h * w * seg.stride(3))
+        rows = int(grid_ind.shape[0])
+        dest = out_offs = None
+        n_out = rows
+        if key_points_index is not None:
+            if out_offsets is None or out_total is None:
+                raise ValueError("predict_panoptic_sweep: key_points_index needs out_offsets and out_total")
+            hip.require_device(key_points_index, out_offsets)
+            dest, out_offs, n_out = key_points_index, out_offsets, int(out_total)
+            assert dest.dtype == torch.int64 and dest.dim() == 1 and dest.is_contiguous() and dest.shape[0] == rows, \
+                "key_points_index must be a contiguous int64 tensor with one entry per grid_ind row"
+            assert out_offs.dtype == torch.int32 and out_offs.dim() == 1 and out_offs.is_contiguous() and out_offs.shape[0] == bs + 1, \
+                "out_offsets must be a contiguous int32 (bs + 1,) tensor"
+        labels = torch.empty((n_out,), dtype=torch.int64, device=dev)
+        if dets is None:
+            hip.call("pn_panoptic_points_sweep_f32", seg.data_ptr(), seg.stride(0) if total > 1 else 0, nsec, bs, h, w, ncls, seg.stride(3),
+                     grid_ind.data_ptr(), offsets.data_ptr(), rows, None, 0, 0, None, None, 0.0, hip.ptr(dest), hip.ptr(out_offs), n_out, labels.data_ptr(), None,
+                     hip.stream())
+            return labels, None
+        sem2box = self._sem2box(class_names, semantic2box, ncls, dev)
+        x_col = 3 if voxel_shape == "cylinder" else 0
+        hip.require_device(points)
+        assert points.dim() == 2 and points.dtype == torch.float32 and points.shape[1] >= x_col + 2
+        if points.numel() and points.stride(1) != 1:
+            points = points.contiguous()
+        assert rows <= points.shape[0], "valid_grid_ind has more rows than the point list: it must hold one row per point"
+        point_stride = points.stride(0) if points.shape[0] > 1 else points.shape[1]
+        interval = None
+        jobs = (hip.PanopticSectorJob * nsec)()
+        for s, det in enumerate(dets):
+            if not (isinstance(det, dict) and "instances" in det and "count" in det):
+                raise TypeError("predict_panoptic_sweep: every sector's list must be the device list of CenterHead.predict(device_only=True) under test_cfg.panoptic")
+            hip.require_device(*det.values())
+            boxes = det["box3d_lidar"]
+            cap = int(boxes.shape[1])
+            assert boxes.dim() == 3 and boxes.shape[0] == bs and boxes.dtype == torch.float32 and boxes.stride(2) == 1 and boxes.stride(0) == cap * boxes.stride(1)
+            for k, dt in (("scores", torch.float32), ("label_preds", torch.int64), ("instances", torch.int64)):
+                assert tuple(det[k].shape) == (bs, cap) and det[k].dtype == dt and det[k].is_contiguous(), f"the device list's '{k}' must be a contiguous (B, cap) tensor"
+            assert tuple(det["count"].shape) == (bs,) and det["count"].dtype == torch.int32
+            angle = 0.0
+            if s > 0:
+                if interval is None:
+                    interval = float(test_cfg.get("interval") if hasattr(test_cfg, "get") else getattr(test_cfg, "interval"))
+                angle = interval * s if voxel_shape == "cylinder" else 2 * math.pi / interval * s
+            j = jobs[s]
+            j.boxes, j.scores, j.label_preds, j.instances, j.count = (boxes.data_ptr(), det["scores"].data_ptr(), det["label_preds"].data_ptr(),
+                                                                      det["instances"].data_ptr(), det["count"].data_ptr())
+            j.box_stride, j.cap, j.cos_a, j.sin_a = boxes.stride(1), cap, math.cos(angle), math.sin(angle)
+        ins = torch.empty((n_out,), dtype=torch.int64, device=dev)
+        hip.call("pn_panoptic_points_sweep_f32", seg.data_ptr(), seg.stride(0) if total > 1 else 0, nsec, bs, h, w, ncls, seg.stride(3), grid_ind.data_ptr(),
+                 offsets.data_ptr(), rows, points.data_ptr(), point_stride, x_col, jobs, sem2box.data_ptr(), float(score_thr), hip.ptr(dest),
+                 hip.ptr(out_offs), n_out, labels.data_ptr(), ins.data_ptr(), hip.stream())
+        return labels, ins
+
     def _sem2box(self, class_names, semantic2box, ncls, dev):
         """DEVICE int32 table semantic label -> box label (-1: stuff), cached on the head per (class names, device): uploaded once"""
         names = [n for sub in class_names for n in ([sub] if isinstance(sub, str) else sub)]
