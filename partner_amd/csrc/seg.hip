@@ -84,63 +84,44 @@ __global__ void bilinear_up_add_bwd_kernel(const float* __restrict__ d_out, int 
   }
 }
 
-// label of point i = 1 + argmax_c seg[b, y, x, c] at the point's BEV cell (first maximum, as torch.argmax);
-// grid_ind rows are [z, y(theta), x(r)] as the reference's valid_grid_ind (seg_head.py:186-192, 2-D prediction map)
-__global__ void seg_point_labels_kernel(const float* __restrict__ seg, int H, int W, int C, const int64_t* __restrict__ grid_ind, int n,
-                                        int64_t* __restrict__ labels) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int64_t y = grid_ind[(size_t)i * 3 + 1], x = grid_ind[(size_t)i * 3 + 2];
-  if (y < 0 || y >= H || x < 0 || x >= W) { labels[i] = 0; return; }
-  const float* p = seg + ((size_t)y * W + x) * C;
-  float best = p[0];
-  int arg = 0;
-  for (int c = 1; c < C; ++c)
-    if (p[c] > best) { best = p[c]; arg = c; }
-  labels[i] = arg + 1;
-}
-
-// Panoptic fusion of one sample (SingleConvHead.predict_panoptic, seg_head.py:99-168): the label gather of seg_point_labels_kernel
-// fused with the nearest-box search.  A point with a thing label takes the instance id of the nearest box centre among the boxes of
-// its class with score > thr; stuff points, points outside the map and things without an eligible box get 0.
-// One lane owns one point; the block stages the boxes chunk by chunk into LDS as (x, y, label or -1 when the score is not above the
-// threshold) in their original order, and every lane scans the chunk: all lanes read the same entry (one 16-byte broadcast read, no
-// bank conflict).  The winner is kept as its ROW, the int64 id is fetched once at the end.  Squared distances, strict '<': the first
-// of equal distances wins, as torch.argmin.  256 threads and 1024 boxes (16 KiB of LDS) per block: 8 blocks fit a CU's LDS, so the
+// The per-point work of the label and panoptic kernels, written once (SingleConvHead.predict / predict_panoptic, seg_head.py:99-195).
+// A point's label is 1 + argmax_c of the logits at its BEV cell (first maximum, as torch.argmax), 0 outside the map; grid_ind rows are
+// [z, y(theta), x(r)] as the reference's valid_grid_ind (2-D prediction map).  Panoptic fusion: a point with a thing label takes the
+// instance id of the nearest box centre among the boxes of its class with score > thr; stuff points, points outside the map and things
+// without an eligible box get 0.  One lane owns one point; the block stages the boxes chunk by chunk into LDS as (x, y, label or -1 when
+// the box is not eligible) in their original order, and every lane scans the chunk: all lanes read the same entry (one 16-byte broadcast
+// read, no bank conflict).  The winner is kept as its ROW, the int64 id is fetched once at the end.  Squared distances, strict '<': the
+// first of equal distances wins, as torch.argmin.  256 threads and 1024 boxes (16 KiB of LDS) per block: 8 blocks fit a CU's LDS, so the
 // wave slots, not the LDS, bound the occupancy; the sweep's few hundred boxes are one chunk.
 constexpr int kPanopticBlock = 256;
 constexpr int kPanopticChunk = 1024;
 
-__global__ __launch_bounds__(kPanopticBlock) void panoptic_points_kernel(
-    const float* __restrict__ seg, int H, int W, int C, int pixel_stride, const int64_t* __restrict__ grid_ind, int n,
-    const float* __restrict__ points, int point_stride, int x_col, float cos_a, float sin_a, const float* __restrict__ boxes, int box_stride,
-    const float* __restrict__ scores, const int64_t* __restrict__ box_labels, const int64_t* __restrict__ instances, int m,
-    const int32_t* __restrict__ sem2box, float score_thr, int64_t* __restrict__ labels, int64_t* __restrict__ instance) {
-  __shared__ float4 sbox[kPanopticChunk];
-  const int i = blockIdx.x * kPanopticBlock + threadIdx.x;
-  int want = -1;          // box label this point looks for; -1: stuff, outside the map, or past the end
-  float px = 0.f, py = 0.f;
-  if (i < n) {
-    const int64_t y = grid_ind[(size_t)i * 3 + 1], x = grid_ind[(size_t)i * 3 + 2];
-    int lab = 0;
-    if (y >= 0 && y < H && x >= 0 && x < W) {
-      const float* p = seg + ((size_t)y * W + x) * pixel_stride;
-      float top = p[0];
-      int arg = 0;
-      for (int c = 1; c < C; ++c)
-        if (p[c] > top) { top = p[c]; arg = c; }
-      lab = arg + 1;
-      want = sem2box[lab];
-    }
-    labels[i] = lab;
-    if (want >= 0) {
-      // the sector's points into the sweep's frame: points[:, x:x+2] @ [[cos, sin], [-sin, cos]] in f32 (seg_head.py:124-127, 159)
-      const float* q = points + (size_t)i * point_stride + x_col;
-      const float qx = q[0], qy = q[1];
-      px = qx * cos_a - qy * sin_a;
-      py = qx * sin_a + qy * cos_a;
-    }
-  }
+// -> the label of the point at cell (y, x): 0 outside the H x W map, else 1 + the first maximum of the cell's C logits (cells are
+// pixel_stride floats apart).  on_map(label) runs for a point on the map only: the panoptic kernels look up its box class there.
+template <class OnMap>
+__device__ __forceinline__ int point_label(const float* __restrict__ seg, int H, int W, int C, int pixel_stride, int64_t y, int64_t x, OnMap on_map) {
+  if (y < 0 || y >= H || x < 0 || x >= W) return 0;
+  const float* p = seg + ((size_t)y * W + x) * pixel_stride;
+  float top = p[0];
+  int arg = 0;
+  for (int c = 1; c < C; ++c)
+    if (p[c] > top) { top = p[c]; arg = c; }
+  on_map(arg + 1);
+  return arg + 1;
+}
+
+// a sector's point into the sweep's frame: q[0:2] @ [[cos, sin], [-sin, cos]] in f32 (seg_head.py:124-127, 159)
+__device__ __forceinline__ void to_sweep_frame(const float* __restrict__ q, float cos_a, float sin_a, float& px, float& py) {
+  const float qx = q[0], qy = q[1];
+  px = qx * cos_a - qy * sin_a;
+  py = qx * sin_a + qy * cos_a;
+}
+
+// -> the row of the eligible box of label `want` nearest to (px, py), -1 without one.  EVERY lane of the block calls this with the
+// same list (the barriers), lanes without a query with want = -1.
+__device__ __forceinline__ int nearest_box_row(const float* __restrict__ boxes, int box_stride, const float* __restrict__ scores,
+                                               const int64_t* __restrict__ box_labels, int m, float score_thr, int want, float px, float py,
+                                               float4* sbox) {
   float best = 0.f;
   int best_row = -1;
   for (int c0 = 0; c0 < m; c0 += kPanopticChunk) {
@@ -164,12 +145,37 @@ __global__ __launch_bounds__(kPanopticBlock) void panoptic_points_kernel(
       }
     }
   }
+  return best_row;
+}
+
+// pn_seg_point_labels: one sample's n rows, logits of exactly C floats per cell
+__global__ void seg_point_labels_kernel(const float* __restrict__ seg, int H, int W, int C, const int64_t* __restrict__ grid_ind, int n,
+                                        int64_t* __restrict__ labels) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  labels[i] = point_label(seg, H, W, C, C, grid_ind[(size_t)i * 3 + 1], grid_ind[(size_t)i * 3 + 2], [](int) {});
+}
+
+// pn_panoptic_points_f32: one sample, every size and the box list's length from the host
+__global__ __launch_bounds__(kPanopticBlock) void panoptic_points_kernel(
+    const float* __restrict__ seg, int H, int W, int C, int pixel_stride, const int64_t* __restrict__ grid_ind, int n,
+    const float* __restrict__ points, int point_stride, int x_col, float cos_a, float sin_a, const float* __restrict__ boxes, int box_stride,
+    const float* __restrict__ scores, const int64_t* __restrict__ box_labels, const int64_t* __restrict__ instances, int m,
+    const int32_t* __restrict__ sem2box, float score_thr, int64_t* __restrict__ labels, int64_t* __restrict__ instance) {
+  __shared__ float4 sbox[kPanopticChunk];
+  const int i = blockIdx.x * kPanopticBlock + threadIdx.x;
+  int want = -1;          // box label this point looks for; -1: stuff, outside the map, or past the end
+  float px = 0.f, py = 0.f;
+  if (i < n) {
+    labels[i] = point_label(seg, H, W, C, pixel_stride, grid_ind[(size_t)i * 3 + 1], grid_ind[(size_t)i * 3 + 2], [&](int lab) { want = sem2box[lab]; });
+    if (want >= 0) to_sweep_frame(points + (size_t)i * point_stride + x_col, cos_a, sin_a, px, py);
+  }
+  const int best_row = nearest_box_row(boxes, box_stride, scores, box_labels, m, score_thr, want, px, py, sbox);
   if (i < n) instance[i] = best_row >= 0 ? instances[best_row] : 0;
 }
 
-// The panoptic fusion of ALL samples of a sector in one launch (SingleConvHead.predict_panoptic(device_only=True)): the per-lane
-// arithmetic of panoptic_points_kernel, unchanged -- gather, argmax, rotation, chunked LDS box scan with strict '<' -- with every
-// count read from device memory, so that a streamed sweep never goes to the host.  blockIdx.y = sample; its point rows are
+// pn_panoptic_points_batched_f32 (SingleConvHead.predict / predict_panoptic(device_only=True)): ALL samples of a sector in one launch,
+// every count read from device memory, so that a streamed sweep never goes to the host.  blockIdx.y = sample; its point rows are
 // [offsets[b], offsets[b + 1]) of the flat arrays, its boxes the first count[b] rows of the (B, cap, .) detection list.  The grid's x
 // extent covers the flat row count (the host knows no sample's own): blocks past a sample's point count leave before the first
 // barrier, and count[b] is uniform across a block, so the barriers of the box scan stay legal.  kBoxes = false: labels only.
@@ -195,63 +201,22 @@ __global__ __launch_bounds__(kPanopticBlock) void panoptic_points_batched_kernel
   int want = -1;
   float px = 0.f, py = 0.f;
   if (i < n) {
-    const int64_t y = a.grid_ind[row * 3 + 1], x = a.grid_ind[row * 3 + 2];
-    int lab = 0;
-    if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
-      const float* p = a.seg + (size_t)b * a.sample_stride + ((size_t)y * a.W + x) * a.pixel_stride;
-      float top = p[0];
-      int arg = 0;
-      for (int c = 1; c < a.C; ++c)
-        if (p[c] > top) { top = p[c]; arg = c; }
-      lab = arg + 1;
-      if (kBoxes) want = a.sem2box[lab];
-    }
+    const int lab = point_label(a.seg + (size_t)b * a.sample_stride, a.H, a.W, a.C, a.pixel_stride, a.grid_ind[row * 3 + 1], a.grid_ind[row * 3 + 2],
+                                [&](int l) { if (kBoxes) want = a.sem2box[l]; });
     a.labels[row] = lab;
-    if (kBoxes && want >= 0) {
-      const float* q = a.points + row * a.point_stride + a.x_col;
-      const float qx = q[0], qy = q[1];
-      px = qx * a.cos_a - qy * a.sin_a;
-      py = qx * a.sin_a + qy * a.cos_a;
-    }
+    if (kBoxes && want >= 0) to_sweep_frame(a.points + row * a.point_stride + a.x_col, a.cos_a, a.sin_a, px, py);
   }
   if (!kBoxes) return;
-  const int m = min(max(a.count[b], 0), a.cap);
-  const float* boxes = a.boxes + (size_t)b * a.cap * a.box_stride;
-  const float* scores = a.scores + (size_t)b * a.cap;
-  const int64_t* box_labels = a.box_labels + (size_t)b * a.cap;
-  const int64_t* instances = a.instances + (size_t)b * a.cap;
-  float best = 0.f;
-  int best_row = -1;
-  for (int c0 = 0; c0 < m; c0 += kPanopticChunk) {
-    const int cnt = min(kPanopticChunk, m - c0);
-    if (c0) __syncthreads();      // every lane is done with the previous chunk
-    for (int j = threadIdx.x; j < cnt; j += kPanopticBlock) {
-      const size_t r = (size_t)(c0 + j);
-      const int64_t bl = box_labels[r];
-      const int lab = (scores[r] > a.score_thr && bl >= 0 && bl <= 0x7fffffff) ? (int)bl : -1;
-      sbox[j] = make_float4(boxes[r * a.box_stride], boxes[r * a.box_stride + 1], __int_as_float(lab), 0.f);
-    }
-    __syncthreads();
-    if (want >= 0) {
-      for (int j = 0; j < cnt; ++j) {
-        const float4 e = sbox[j];
-        if (__float_as_int(e.z) == want) {
-          const float dx = px - e.x, dy = py - e.y;
-          const float d = dx * dx + dy * dy;
-          if (best_row < 0 || d < best) { best = d; best_row = c0 + j; }
-        }
-      }
-    }
-  }
-  if (i < n) a.instance[row] = best_row >= 0 ? instances[best_row] : 0;
+  const int best_row = nearest_box_row(a.boxes + (size_t)b * a.cap * a.box_stride, a.box_stride, a.scores + (size_t)b * a.cap,
+                                       a.box_labels + (size_t)b * a.cap, min(max(a.count[b], 0), a.cap), a.score_thr, want, px, py, sbox);
+  if (i < n) a.instance[row] = best_row >= 0 ? a.instances[(size_t)b * a.cap + best_row] : 0;
 }
 
-// The panoptic fusion of a whole SWEEP in one launch (SingleConvHead.predict_panoptic_sweep; PolarStreamBDCP has every sector's logits
-// before its first NMS runs, and every sector's detection list is a buffer of its own, so the per-point work does not depend on the
-// sector loop).  blockIdx.y = k = s * bs + b, the stacked (sector-major) sample: logits seg + k * sample_stride, point rows
+// pn_panoptic_points_sweep_f32 (SingleConvHead.predict_panoptic_sweep; PolarStreamBDCP has every sector's logits before its first NMS
+// runs, and every sector's detection list is a buffer of its own, so the per-point work does not depend on the sector loop): a whole
+// SWEEP in one launch.  blockIdx.y = k = s * bs + b, the stacked (sector-major) sample: logits seg + k * sample_stride, point rows
 // [offsets[k], offsets[k + 1]), the boxes of row b of sector s's list and sector s's rotation -- the job table travels in the kernel
-// arguments, nothing is uploaded.  Per lane the code of panoptic_points_batched_kernel, statement for statement: sector s of this launch
-// and the batched launch on (seg + s * bs * sample_stride, offsets + s * bs, sector s's list) write the same bits.
+// arguments, nothing is uploaded.
 // dest != NULL: dataset order -- row `row` of sample b goes to out[out_offsets[b] + dest[row]] (single_stage.py:118-128, the
 // key_points_index scatter), dropped when dest[row] lies outside [0, out_offsets[b + 1] - out_offsets[b]) or the slot outside
 // [0, out_total); the entry zero-fills the outputs first.
@@ -269,6 +234,8 @@ struct PanopticSweep {
   int64_t* labels; int64_t* instance;
   SweepJob job[kMaxSweepSectors];
 };
+// the kernel-argument budget of the two launches: the 32-entry table rides on the sweep launch alone
+static_assert(sizeof(PanopticBatch) <= 160 && sizeof(PanopticSweep) <= 1928, "the kernel arguments of the panoptic launches grew");
 
 template <bool kBoxes>
 __global__ __launch_bounds__(kPanopticBlock) void panoptic_points_sweep_kernel(PanopticSweep a) {
@@ -292,58 +259,22 @@ __global__ __launch_bounds__(kPanopticBlock) void panoptic_points_sweep_kernel(P
   int want = -1;
   float px = 0.f, py = 0.f;
   if (i < n) {
-    const int64_t y = a.grid_ind[row * 3 + 1], x = a.grid_ind[row * 3 + 2];
-    int lab = 0;
-    if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
-      const float* p = a.seg + (size_t)k * a.sample_stride + ((size_t)y * a.W + x) * a.pixel_stride;
-      float top = p[0];
-      int arg = 0;
-      for (int c = 1; c < a.C; ++c)
-        if (p[c] > top) { top = p[c]; arg = c; }
-      lab = arg + 1;
-      if (kBoxes) want = a.sem2box[lab];
-    }
+    const int lab = point_label(a.seg + (size_t)k * a.sample_stride, a.H, a.W, a.C, a.pixel_stride, a.grid_ind[row * 3 + 1], a.grid_ind[row * 3 + 2],
+                                [&](int l) { if (kBoxes) want = a.sem2box[l]; });
     if (keep) a.labels[at] = lab;
-    if (kBoxes && want >= 0) {
-      const float* q = a.points + row * a.point_stride + a.x_col;
-      const float qx = q[0], qy = q[1];
-      px = qx * cos_a - qy * sin_a;
-      py = qx * sin_a + qy * cos_a;
-    }
+    if (kBoxes && want >= 0) to_sweep_frame(a.points + row * a.point_stride + a.x_col, cos_a, sin_a, px, py);
   }
   if (!kBoxes) return;
   const SweepJob& job = a.job[s];
-  const int cap = job.cap, box_stride = job.box_stride;
-  const int m = min(max(job.count[b], 0), cap);
-  const float* boxes = job.boxes + (size_t)b * cap * box_stride;
-  const float* scores = job.scores + (size_t)b * cap;
-  const int64_t* box_labels = job.box_labels + (size_t)b * cap;
-  const int64_t* instances = job.instances + (size_t)b * cap;
-  float best = 0.f;
-  int best_row = -1;
-  for (int c0 = 0; c0 < m; c0 += kPanopticChunk) {
-    const int cnt = min(kPanopticChunk, m - c0);
-    if (c0) __syncthreads();      // every lane is done with the previous chunk
-    for (int j = threadIdx.x; j < cnt; j += kPanopticBlock) {
-      const size_t r = (size_t)(c0 + j);
-      const int64_t bl = box_labels[r];
-      const int lab = (scores[r] > a.score_thr && bl >= 0 && bl <= 0x7fffffff) ? (int)bl : -1;
-      sbox[j] = make_float4(boxes[r * box_stride], boxes[r * box_stride + 1], __int_as_float(lab), 0.f);
-    }
-    __syncthreads();
-    if (want >= 0) {
-      for (int j = 0; j < cnt; ++j) {
-        const float4 e = sbox[j];
-        if (__float_as_int(e.z) == want) {
-          const float dx = px - e.x, dy = py - e.y;
-          const float d = dx * dx + dy * dy;
-          if (best_row < 0 || d < best) { best = d; best_row = c0 + j; }
-        }
-      }
-    }
-  }
-  if (keep) a.instance[at] = best_row >= 0 ? instances[best_row] : 0;
+  const int cap = job.cap;
+  const int best_row = nearest_box_row(job.boxes + (size_t)b * cap * job.box_stride, job.box_stride, job.scores + (size_t)b * cap,
+                                       job.box_labels + (size_t)b * cap, min(max(job.count[b], 0), cap), a.score_thr, want, px, py, sbox);
+  if (keep) a.instance[at] = best_row >= 0 ? job.instances[(size_t)b * cap + best_row] : 0;
 }
+
+// argument checks the entries share (each entry keeps its own message)
+inline bool map_ok(int h, int w, int classes, int pixel_stride) { return h >= 1 && w >= 1 && classes >= 1 && pixel_stride >= classes; }
+inline bool point_columns_ok(int x_col, int point_stride) { return x_col >= 0 && point_stride >= x_col + 2; }
 
 }  // namespace
 
@@ -370,7 +301,7 @@ int pn_bilinear_upsample_add_bwd_f32(const float* d_out, int batch, int h, int w
 }
 
 int pn_seg_point_labels(const float* seg_sample, int h, int w, int classes, const int64_t* grid_ind, int n, int64_t* labels, pn_stream_t stream) {
-  PN_REQUIRE(seg_sample && labels && h >= 1 && w >= 1 && classes >= 1 && n >= 0, "seg_point_labels: bad arguments");
+  PN_REQUIRE(seg_sample && labels && map_ok(h, w, classes, classes) && n >= 0, "seg_point_labels: bad arguments");
   if (n == 0) return PN_OK;
   PN_REQUIRE(grid_ind != nullptr, "seg_point_labels: null grid_ind");
   hipLaunchKernelGGL(seg_point_labels_kernel, dim3(pn::cdiv(n, 256)), dim3(256), 0, pn::S(stream), seg_sample, h, w, classes, grid_ind, n, labels);
@@ -381,10 +312,10 @@ int pn_panoptic_points_f32(const float* seg_sample, int h, int w, int classes, i
                            int point_stride, int x_col, float cos_a, float sin_a, const float* boxes, int box_stride, const float* scores,
                            const int64_t* box_labels, const int64_t* instances, int m, const int32_t* sem2box, float score_thr, int64_t* labels,
                            int64_t* instance, pn_stream_t stream) {
-  PN_REQUIRE(h >= 1 && w >= 1 && classes >= 1 && pixel_stride >= classes && n >= 0 && m >= 0, "panoptic_points: bad arguments");
+  PN_REQUIRE(map_ok(h, w, classes, pixel_stride) && n >= 0 && m >= 0, "panoptic_points: bad arguments");
   if (n == 0) return PN_OK;
   PN_REQUIRE(seg_sample && grid_ind && points && sem2box && labels && instance, "panoptic_points: null pointer");
-  PN_REQUIRE(x_col >= 0 && point_stride >= x_col + 2, "panoptic_points: the point rows must hold columns x_col and x_col + 1");
+  PN_REQUIRE(point_columns_ok(x_col, point_stride), "panoptic_points: the point rows must hold columns x_col and x_col + 1");
   PN_REQUIRE(m == 0 || (boxes && scores && box_labels && instances && box_stride >= 2), "panoptic_points: null box arrays or box_stride < 2");
   hipLaunchKernelGGL(panoptic_points_kernel, dim3(pn::cdiv(n, kPanopticBlock)), dim3(kPanopticBlock), 0, pn::S(stream), seg_sample, h, w, classes,
                      pixel_stride, grid_ind, n, points, point_stride, x_col, cos_a, sin_a, boxes, box_stride, scores, box_labels, instances, m, sem2box,
@@ -397,7 +328,7 @@ int pn_panoptic_points_batched_f32(const float* seg, long long sample_stride, in
                                    float cos_a, float sin_a, const float* boxes, int box_stride, int capacity, const float* scores,
                                    const int64_t* box_labels, const int64_t* instances, const int32_t* count, const int32_t* sem2box, float score_thr,
                                    int64_t* labels, int64_t* instance, pn_stream_t stream) {
-  PN_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && classes >= 1 && pixel_stride >= classes && n_total >= 0 && sample_stride >= 0,
+  PN_REQUIRE(batch >= 1 && batch <= 65535 && map_ok(h, w, classes, pixel_stride) && n_total >= 0 && sample_stride >= 0,
              "panoptic_points_batched: bad arguments");
   if (n_total == 0) return PN_OK;
   PN_REQUIRE(seg && grid_ind && offsets && labels, "panoptic_points_batched: null pointer");
@@ -410,7 +341,7 @@ int pn_panoptic_points_batched_f32(const float* seg, long long sample_stride, in
     return pn::check_launch("panoptic_points_batched_kernel<labels>");
   }
   PN_REQUIRE(points && sem2box && instance && scores && box_labels && instances && count, "panoptic_points_batched: null pointer");
-  PN_REQUIRE(x_col >= 0 && point_stride >= x_col + 2, "panoptic_points_batched: the point rows must hold columns x_col and x_col + 1");
+  PN_REQUIRE(point_columns_ok(x_col, point_stride), "panoptic_points_batched: the point rows must hold columns x_col and x_col + 1");
   PN_REQUIRE(capacity >= 1 && box_stride >= 2, "panoptic_points_batched: capacity < 1 or box_stride < 2");
   a.points = points; a.point_stride = point_stride; a.x_col = x_col; a.cos_a = cos_a; a.sin_a = sin_a;
   a.boxes = boxes; a.box_stride = box_stride; a.cap = capacity; a.scores = scores; a.box_labels = box_labels; a.instances = instances; a.count = count;
@@ -425,8 +356,7 @@ int pn_panoptic_points_sweep_f32(const float* seg, long long sample_stride, int 
                                  const int32_t* out_offsets, long long out_total, int64_t* labels, int64_t* instance, pn_stream_t stream) {
   PN_REQUIRE(nsectors >= 1 && nsectors <= kMaxSweepSectors && batch >= 1 && (long long)nsectors * batch <= 65535,
              "panoptic_points_sweep: 1..32 sectors, at most 65535 stacked samples");
-  PN_REQUIRE(h >= 1 && w >= 1 && classes >= 1 && pixel_stride >= classes && n_total >= 0 && sample_stride >= 0 && out_total >= 0,
-             "panoptic_points_sweep: bad arguments");
+  PN_REQUIRE(map_ok(h, w, classes, pixel_stride) && n_total >= 0 && sample_stride >= 0 && out_total >= 0, "panoptic_points_sweep: bad arguments");
   PN_REQUIRE(seg && offsets && labels && (grid_ind || n_total == 0), "panoptic_points_sweep: null pointer");
   PN_REQUIRE(!dest || out_offsets, "panoptic_points_sweep: dest (dataset order) needs out_offsets");
   PanopticSweep a{};
@@ -435,7 +365,7 @@ int pn_panoptic_points_sweep_f32(const float* seg, long long sample_stride, int 
   a.dest = dest; a.out_offsets = dest ? out_offsets : nullptr; a.out_total = out_total;
   if (jobs) {
     PN_REQUIRE((points || n_total == 0) && sem2box && instance, "panoptic_points_sweep: null pointer");
-    PN_REQUIRE(x_col >= 0 && point_stride >= x_col + 2, "panoptic_points_sweep: the point rows must hold columns x_col and x_col + 1");
+    PN_REQUIRE(point_columns_ok(x_col, point_stride), "panoptic_points_sweep: the point rows must hold columns x_col and x_col + 1");
     for (int s = 0; s < nsectors; ++s) {
       const pn_panoptic_sector_job& j = jobs[s];
       PN_REQUIRE(j.boxes && j.scores && j.label_preds && j.instances && j.count, "panoptic_points_sweep: null pointer in sector %d's list", s);

@@ -19,6 +19,7 @@ from .builder import DETECTORS
 from .nn_utils import eval_only
 from .readers import DynamicPFNet
 from .routes import R, S
+from .seg_heads import SingleConvHead, device_offsets, host_counts, merge_per_token, prefix_sums, sample_token
 
 
 @DETECTORS.register_module
@@ -300,21 +301,7 @@ class PolarStream(PointPillars):
         if isinstance(example, dict):
             return self.forward_one_sector(example, return_loss, **kwargs)
         stateful, panoptic = self._test_flag("stateful_nms"), self._test_flag("panoptic")
-        if kwargs.get("device_only", False) and not return_loss and not kwargs.get("raw_preds", False) and self.test_cfg is not None:
-            rets, prev = [], []
-            for i, ex in enumerate(example):
-                kw = dict(kwargs, prev_context=prev, sec_id=i)
-                if (stateful or panoptic) and i > 0:
-                    kw["prev_dets"] = rets[-1]["det"]
-                r = self.forward_one_sector(ex, False, **kw)
-                prev = r.pop("next_context", []) if i < len(example) - 1 else []
-                r.pop("next_context", None)
-                rets.append(r)
-            out = {"det": rets[-1]["det"] if (stateful or panoptic) else [r["det"] for r in rets]}
-            for k in ("seg", "ins"):
-                if k in rets[0]:
-                    out[k] = [r[k] for r in rets]
-            return out
+        dev_only = bool(kwargs.get("device_only", False)) and not return_loss and not kwargs.get("raw_preds", False) and self.test_cfg is not None
         rets, prev = [], []
         for i, ex in enumerate(example):
             kw = dict(kwargs, prev_context=prev, sec_id=i)
@@ -323,9 +310,15 @@ class PolarStream(PointPillars):
             r = self.forward_one_sector(ex, return_loss, **kw)
             prev = r.pop("next_context", []) if i < len(example) - 1 else []
             r.pop("next_context", None)
-            if "key_points_index" in ex:          # polarstream.py:99-100
+            if "key_points_index" in ex and not dev_only:      # polarstream.py:99-100; the device form leaves the order to sweep_to_host
                 r["key_points_index"] = ex["key_points_index"]
             rets.append(r)
+        if dev_only:
+            out = {"det": rets[-1]["det"] if (stateful or panoptic) else [r["det"] for r in rets]}
+            for k in ("seg", "ins"):
+                if k in rets[0]:
+                    out[k] = [r[k] for r in rets]
+            return out
         out = self.merge_sectors(rets, len(example[-1]["num_points"]), stateful or panoptic)
         if (stateful or panoptic) and "det" in out:
             for det, meta in zip(out["det"], example[-1].get("metadata", [None] * len(out["det"]))):
@@ -362,18 +355,11 @@ class PolarStream(PointPillars):
         for key in ("seg", "ins"):
             if key not in out:
                 continue
-            batch = len(examples[0]["num_points"])
-            merged = [{} for _ in range(batch)]
-            for ex, flat in zip(examples, out[key]):
-                num = ex["num_points"]
-                num = [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
-                start = 0
-                for i, n in enumerate(num):
-                    meta = ex["metadata"][i]
-                    token = meta["token"] if isinstance(meta, dict) and "token" in meta else i
-                    merged[i].setdefault(token, []).append(flat[start:start + n])
-                    start += n
-            res[key] = [{token: torch.cat(v) for token, v in m.items()} for m in merged]
+            sectors = []
+            for ex, flat in zip(examples, out[key]):      # a sector's flat rows cut into its samples' by the host counts
+                acc = prefix_sums(host_counts(ex["num_points"]))
+                sectors.append([{sample_token(ex["metadata"], i): flat[lo:hi]} for i, (lo, hi) in enumerate(zip(acc[:-1], acc[1:]))])
+            res[key] = merge_per_token(sectors, len(examples[0]["num_points"]))
         if ("seg" in res or "ins" in res) and all("key_points_index" in ex for ex in examples):
             batch = len(examples[0]["num_points"])
             index = [PolarStream._cat_index([ex["key_points_index"][i] for ex in examples]) for i in range(batch)]
@@ -445,12 +431,7 @@ class PolarStream(PointPillars):
             elif k in ("det_preds", "seg_preds"):
                 out[k] = vals
             elif k in ("seg", "ins"):
-                merged = [{} for _ in range(batch_size)]
-                for sec in vals:
-                    for i in range(batch_size):
-                        for token, v in sec[i].items():
-                            merged[i].setdefault(token, []).append(v)
-                out[k] = [{token: torch.cat(v) for token, v in m.items()} for m in merged]
+                out[k] = merge_per_token(vals, batch_size)
             elif k == "key_points_index":
                 out[k] = [PolarStream._cat_index([sec[i] for sec in vals]) for i in range(batch_size)]
         if "key_points_index" in out:
@@ -554,6 +535,20 @@ class PolarStreamBDCP(PolarStream):
             raise NotImplementedError("PolarStreamBDCP: test_cfg.panoptic (polarstream.py:423-460) needs a seg head -- the panoptic fusion assigns the "
                                       "boxes' instance ids to the seg head's per-point labels")
 
+    def _sector(self, preds, example, i, bs, per_point=False):
+        """sector i's slice of the stacked predictions and of the stacked example: 'metadata', 'pc_range' (when the example has one) and,
+        ``per_point``, 'num_points' / 'valid_grid_ind' -> (preds, example)"""
+        cut = slice(i * bs, (i + 1) * bs)
+        pr = {"det_preds": [{k: v[cut] for k, v in t.items()} for t in preds["det_preds"]]}
+        if "seg_preds" in preds:
+            pr["seg_preds"] = preds["seg_preds"][cut]
+        ex = dict(metadata=example.get("metadata", [None] * (self.nsectors * bs))[cut])
+        if "pc_range" in example:
+            ex["pc_range"] = example["pc_range"][cut]
+        if per_point:
+            ex.update({k: example[k][cut] for k in ("num_points", "valid_grid_ind")})
+        return pr, ex
+
     def forward_one_sweep(self, example, mode="feature_only", return_loss=False, **kwargs):
         self._refuse_unbuilt(return_loss)
         canvas, batch = self._canvas(example)
@@ -564,30 +559,22 @@ class PolarStreamBDCP(PolarStream):
             return self.warp_prev_sweep(cur, torch.as_tensor(example["transform_matrix"])[:bs], bs)
         x2 = self._stream_sectors(canvas, kwargs["prev_sweep"], bs, mode)
         preds = self._heads(canvas, x2)             # polarstream.py:404-408: the seg head (when there is one) on the stacked canvases + neck output
-        cut = lambda i: {"det_preds": [{k: v[i * bs:(i + 1) * bs] for k, v in t.items()} for t in preds["det_preds"]],  # noqa: E731
-                         **({"seg_preds": preds["seg_preds"][i * bs:(i + 1) * bs]} if "seg_preds" in preds else {})}
         if kwargs.get("raw_preds", False) or self.test_cfg is None:
-            return [cut(i) for i in range(nsec)]
+            return [self._sector(preds, example, i, bs)[0] for i in range(nsec)]
         stateful, panoptic = bool(self._get("stateful_nms", False)), self._test_flag("panoptic")
         rets, prev_dets = [], None
-        metas = example.get("metadata", [None] * batch)
         key_index = self._key_index_lists(example) if (self.seg_head is not None and nsec > 1) else None
         cum = 0
         for i in range(nsec):
-            pr = cut(i)
-            ex = dict(metadata=metas[i * bs:(i + 1) * bs])
-            if "pc_range" in example:
-                ex["pc_range"] = example["pc_range"][i * bs:(i + 1) * bs]
+            pr, ex = self._sector(preds, example, i, bs, per_point=self.seg_head is not None)
             det = self.bbox_head.predict(ex, pr, self.test_cfg, sec_id=i, prev_dets=prev_dets)
             rets.append({"det": det})
             prev_dets = det if (stateful or panoptic) and i < nsec - 1 else None      # polarstream.py:444-448
             if self.seg_head is not None:           # polarstream.py:449-463
-                for k in ("num_points", "valid_grid_ind"):
-                    ex[k] = example[k][i * bs:(i + 1) * bs]
                 if key_index is not None:           # :453-454 (one sector: not read)
                     rets[i]["key_points_index"] = key_index[i * bs:(i + 1) * bs]
                 if panoptic:                        # :455-460: the sector's slice of the stacked point list, one row per valid_grid_ind row
-                    n = sum(int(v) for v in ex["num_points"])
+                    n = sum(host_counts(ex["num_points"]))
                     ex["points"] = example["points"][cum:cum + n]
                     cum += n
                     self.seg_head.predict_panoptic(ex, pr, self.test_cfg, rets[i], voxel_shape=self.bbox_head.voxel_shape,
@@ -602,7 +589,7 @@ class PolarStreamBDCP(PolarStream):
         kpi = example.get("key_points_index")
         if kpi is None or not torch.is_tensor(kpi):
             return kpi
-        return list(torch.split(kpi.reshape(-1), self._host_counts(example)))
+        return list(torch.split(kpi.reshape(-1), host_counts(example["num_points"])))
 
     def _key_index_flat(self, example, rows, dev):
         """the device path's form of ``example['key_points_index']``: ONE (rows,) int64 device tensor in stacked row order.  A device tensor
@@ -621,44 +608,13 @@ class PolarStreamBDCP(PolarStream):
     def _sample_offsets(self, example, dev):
         """(bs + 1,) int32 device offsets of the samples' points in dataset order (a sample's points of all sectors together) and their
         host values: ``example['sample_offsets']`` when present, otherwise built once from the host ``num_points`` and kept there"""
-        num = self._host_counts(example)
+        num = host_counts(example["num_points"])
         bs = len(num) // self.nsectors
-        acc = [0]
-        for b in range(bs):
-            acc.append(acc[-1] + sum(num[b::bs]))
-        offs = example.get("sample_offsets")
-        if offs is None:
-            offs = example["sample_offsets"] = torch.tensor(acc, dtype=torch.int32, device=dev)
-        hip.require_device(offs)
+        acc = prefix_sums(sum(num[b::bs]) for b in range(bs))
+        offs = device_offsets(example, "sample_offsets", acc, dev)
         assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous() and offs.shape[0] == bs + 1, \
             "sample_offsets must be a contiguous int32 (bs + 1,) tensor"
         return offs, acc
-
-    def _point_rows(self, example, dev):
-        """the stacked sweep's per-point grid indices as ONE (rows, 3) int64 device tensor and the (nsectors * bs + 1,) int32 row offsets
-        of its samples: ``example['point_offsets']`` when present, otherwise built once from the host ``num_points`` and kept in the
-        example (an upload: not capturable), as ``SingleConvHead._flat_rows`` does for a sector"""
-        gi = example["valid_grid_ind"]
-        if not torch.is_tensor(gi):
-            hip.require_device(*gi)
-            gi = torch.cat([g.to(torch.int64) for g in gi], 0) if len(gi) > 1 else gi[0]
-        hip.require_device(gi)
-        gi = gi.to(torch.int64).contiguous()
-        offs = example.get("point_offsets")
-        if offs is None:
-            acc = [0]
-            for v in self._host_counts(example):
-                acc.append(acc[-1] + v)
-            offs = example["point_offsets"] = torch.tensor(acc, dtype=torch.int32, device=dev)
-        hip.require_device(offs)
-        assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous() and offs.shape[0] == len(example["num_points"]) + 1, \
-            "point_offsets must be a contiguous int32 (nsectors * bs + 1,) tensor"
-        return gi, offs
-
-    @staticmethod
-    def _host_counts(example):
-        num = example["num_points"]
-        return [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
 
     def prev_sweep_strips(self, example):
         """the previous sweep's pass of the device path: canvas, the neck up to its last layer's input, one strip-warp launch
@@ -685,30 +641,24 @@ class PolarStreamBDCP(PolarStream):
         preds = self._heads(canvas, self._stream_sectors(canvas, prev_sweep, bs, "eval"))
         stateful, panoptic = bool(self._get("stateful_nms", False)), self._test_flag("panoptic")
         carry = stateful or panoptic
-        metas = ex.get("metadata", [None] * batch)
         dets, segs, prev_dets = [], [], None
         ordered = self.seg_head is not None and nsec > 1 and ex.get("key_points_index") is not None
         sweep_launch = panoptic or ordered      # the per-point work of all sectors in one launch after the loop
         if self.seg_head is not None:
-            gi, offs = self._point_rows(ex, canvas.device)
-            first = [0]
-            for v in self._host_counts(ex):
-                first.append(first[-1] + v)
+            gi, offs = SingleConvHead._flat_rows(ex, canvas.device, stacked=True)
+            first = prefix_sums(host_counts(ex["num_points"]))
             if sweep_launch:
                 assert gi.dim() == 2 and gi.shape[1] == 3 and gi.shape[0] == first[-1] <= ex["points"].shape[0], \
                     "valid_grid_ind must hold one [z, y, x] row per point of the stacked point list"
         for i in range(nsec):
-            sec = dict(metadata=metas[i * bs:(i + 1) * bs])
-            if "pc_range" in ex:
-                sec["pc_range"] = ex["pc_range"][i * bs:(i + 1) * bs]
-            pr = {"det_preds": [{k: v[i * bs:(i + 1) * bs] for k, v in t.items()} for t in preds["det_preds"]]}
+            pr, sec = self._sector(preds, ex, i, bs)
             prev_dets = self.bbox_head.predict(sec, pr, self.test_cfg, sec_id=i, prev_dets=prev_dets if carry else None, device_only=True)
             dets.append(prev_dets)
             if self.seg_head is not None and not sweep_launch:
                 # the sector's samples are rows [offs[i * bs], offs[(i + 1) * bs]) of the sweep's flat list: the kernel takes absolute offsets, so
                 # the head gets the whole list with the sector's offsets and writes the sector's rows, which the host counts cut out
                 rows = dict(valid_grid_ind=gi, point_offsets=offs[i * bs:(i + 1) * bs + 1])
-                labels = self.seg_head.predict(rows, {"seg_preds": preds["seg_preds"][i * bs:(i + 1) * bs]}, self.test_cfg, device_only=True)
+                labels = self.seg_head.predict(rows, pr, self.test_cfg, device_only=True)
                 segs.append(labels[first[i * bs]:first[(i + 1) * bs]])
         out = {"det": dets[-1] if carry else dets}
         if sweep_launch:
@@ -736,14 +686,13 @@ class PolarStreamBDCP(PolarStream):
         order (``out['dataset_order']``: one tensor per sample, written at the ``key_points_index`` positions on the device) only need their
         token."""
         nsec = self.nsectors
-        num = self._host_counts(cur_example)
+        num = host_counts(cur_example["num_points"])
         bs = len(num) // nsec
         metas = cur_example.get("metadata", [None] * len(num))
         sectors = [dict(num_points=num[i * bs:(i + 1) * bs], metadata=metas[i * bs:(i + 1) * bs]) for i in range(nsec)]
         per_point = {}
         if out.get("dataset_order", False):
-            tokens = [m["token"] if isinstance(m, dict) and "token" in m else i for i, m in enumerate(metas[:bs])]
-            per_point = {k: [{tokens[i]: t} for i, t in enumerate(out[k])] for k in ("seg", "ins") if k in out}
+            per_point = {k: [{sample_token(metas, i): t} for i, t in enumerate(out[k])] for k in ("seg", "ins") if k in out}
             out = {k: v for k, v in out.items() if k not in ("seg", "ins", "dataset_order")}
         res = PolarStream.sweep_to_host(out, sectors)
         res.update(per_point)

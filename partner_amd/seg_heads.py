@@ -24,6 +24,46 @@ from .nn_utils import PlanCache, eval_only
 SEMANTIC2BOX = ["barrier", "bicycle", "bus", "car", "construction_vehicle", "motorcycle", "pedestrian", "traffic_cone", "trailer", "truck"]
 
 
+def host_counts(num) -> list:
+    """per-sample counts (``example['num_points']``: a list, an array or a tensor) as host ints"""
+    return [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
+
+
+def prefix_sums(counts) -> list:
+    """exclusive prefix sums of ``counts``, the total last: (len(counts) + 1) entries"""
+    acc = [0]
+    for v in counts:
+        acc.append(acc[-1] + v)
+    return acc
+
+
+def device_offsets(example, key, acc, dev) -> torch.Tensor:
+    """``example[key]`` when present, otherwise the host prefix sums ``acc`` as a device int32 tensor, built once and kept in the
+    example under ``key`` (an upload: not capturable)"""
+    offs = example.get(key)
+    if offs is None:
+        offs = example[key] = torch.tensor(acc, dtype=torch.int32, device=dev)
+    hip.require_device(offs)
+    return offs
+
+
+def sample_token(metas, i):
+    """the key of sample i's per-point outputs: its metadata's token, or its position"""
+    meta = metas[i]
+    return meta["token"] if isinstance(meta, dict) and "token" in meta else i
+
+
+def merge_per_token(sectors, batch_size) -> list:
+    """per-sample {token: tensor} dicts of the sectors, in sector order -> per sample one dict, every token's tensors concatenated
+    (single_stage.py:106-116)"""
+    merged = [{} for _ in range(batch_size)]
+    for sec in sectors:
+        for i in range(batch_size):
+            for token, v in sec[i].items():
+                merged[i].setdefault(token, []).append(v)
+    return [{token: torch.cat(v) for token, v in m.items()} for m in merged]
+
+
 def seg_loss_sizes() -> dict:
     """the sizes at which the loss kernels change path: keys per tile of the compaction / radix sort / scan, threads per block, keys ranked
     per step of the radix scatter (one wave)"""
@@ -348,52 +388,79 @@ class SingleConvHead(nn.Module):
                 base = base.contiguous()
             if gi.shape[0]:                                      # a sample without points in this sector (streaming): an empty label tensor
                 hip.call("pn_seg_point_labels", base.data_ptr(), h, w, ncls, gi.data_ptr(), gi.shape[0], labels.data_ptr(), hip.stream())
-            meta = example["metadata"][i]
-            token = meta["token"] if isinstance(meta, dict) and "token" in meta else i
-            out.append({token: labels})
+            out.append({sample_token(example["metadata"], i): labels})
         return out
 
     @staticmethod
-    def _flat_rows(example, dev):
-        """device_only inputs: the sector's grid indices as ONE (rows, 3) int64 tensor (``example['valid_grid_ind']``: that tensor, or the
-        per-sample list, concatenated on the device) and the samples' row offsets, device int32 (B + 1,): ``example['point_offsets']``
-        when present, otherwise built once from the host ``num_points`` and kept in the example (an upload: not capturable)"""
+    def _flat_rows(example, dev, stacked=False):
+        """device_only inputs: the grid indices of a sector -- or, ``stacked``, of PolarStreamBDCP's whole sweep -- as ONE (rows, 3) int64
+        tensor (``example['valid_grid_ind']``: that tensor, or the per-sample list, concatenated on the device) and the samples' row
+        offsets, device int32 (B + 1,): ``example['point_offsets']`` when present, otherwise built once from the host ``num_points`` and
+        kept in the example (an upload: not capturable)"""
         gi = example["valid_grid_ind"]
         if not torch.is_tensor(gi):
             hip.require_device(*gi)
             gi = torch.cat([g.to(torch.int64) for g in gi], 0) if len(gi) > 1 else gi[0]
         hip.require_device(gi)
         gi = gi.to(torch.int64).contiguous()
-        assert gi.dim() == 2 and gi.shape[1] == 3, "valid_grid_ind must hold one [z, y, x] row per point"
-        offs = example.get("point_offsets")
-        if offs is None:
-            num = example["num_points"]
-            num = [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
-            assert sum(num) <= gi.shape[0], "num_points does not match valid_grid_ind"
-            acc = [0]
-            for v in num:
-                acc.append(acc[-1] + v)
-            offs = example["point_offsets"] = torch.tensor(acc, dtype=torch.int32, device=dev)
-        hip.require_device(offs)
-        assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous(), "point_offsets must be a contiguous int32 (B + 1,) tensor"
+        assert stacked or (gi.dim() == 2 and gi.shape[1] == 3), "valid_grid_ind must hold one [z, y, x] row per point"      # stacked: the caller's
+        acc = None
+        if example.get("point_offsets") is None:
+            acc = prefix_sums(host_counts(example["num_points"]))
+            assert stacked or acc[-1] <= gi.shape[0], "num_points does not match valid_grid_ind"
+        offs = device_offsets(example, "point_offsets", acc, dev)
+        well_formed = offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous()
+        if stacked:
+            assert well_formed and offs.shape[0] == len(example["num_points"]) + 1, "point_offsets must be a contiguous int32 (nsectors * bs + 1,) tensor"
+        else:
+            assert well_formed, "point_offsets must be a contiguous int32 (B + 1,) tensor"
         return gi, offs
 
-    def _launch_batched(self, seg, gi, offs, labels, points=None, x_col=0, angle=0.0, det=None, sem2box=None, score_thr=0.0, ins=None):
-        """`pn_panoptic_points_batched_f32` on the (possibly channel-padded) NHWC logits, read in place; det None: labels only"""
+    @staticmethod
+    def _device_list(det, bsz, wrong_type):
+        """checks a device detection list of ``CenterHead.predict(device_only=True)`` under test_cfg.panoptic (TypeError ``wrong_type``
+        when it is none) against the batch size -> the launch's box arguments (boxes, box stride, capacity, scores, labels, instance
+        ids, counts)"""
+        if not (isinstance(det, dict) and "instances" in det and "count" in det):
+            raise TypeError(wrong_type)
+        hip.require_device(*det.values())
+        boxes = det["box3d_lidar"]
+        cap = int(boxes.shape[1])
+        assert boxes.dim() == 3 and boxes.shape[0] == bsz and boxes.dtype == torch.float32 and boxes.stride(2) == 1 and boxes.stride(0) == cap * boxes.stride(1)
+        for k, dt in (("scores", torch.float32), ("label_preds", torch.int64), ("instances", torch.int64)):
+            assert tuple(det[k].shape) == (bsz, cap) and det[k].dtype == dt and det[k].is_contiguous(), f"the device list's '{k}' must be a contiguous (B, cap) tensor"
+        assert tuple(det["count"].shape) == (bsz,) and det["count"].dtype == torch.int32
+        return (boxes.data_ptr(), boxes.stride(1), cap, det["scores"].data_ptr(), det["label_preds"].data_ptr(), det["instances"].data_ptr(),
+                det["count"].data_ptr())
+
+    @staticmethod
+    def _sector_angle(test_cfg, voxel_shape, sec_id):
+        """the rotation of sector ``sec_id``'s points into the sweep's frame: ``interval * sec_id``, cuboid: ``2 pi / interval * sec_id``
+        (sector 0 reads no interval)"""
+        if sec_id <= 0:
+            return 0.0
+        interval = float(test_cfg.get("interval") if hasattr(test_cfg, "get") else getattr(test_cfg, "interval"))
+        return interval * sec_id if voxel_shape == "cylinder" else 2 * math.pi / interval * sec_id
+
+    @staticmethod
+    def _point_list(points, x_col):
+        """the device point list with the Cartesian (x, y) in columns x_col, x_col + 1 -> (the list with unit inner stride, its row stride)"""
+        hip.require_device(points)
+        assert points.dim() == 2 and points.dtype == torch.float32 and points.shape[1] >= x_col + 2
+        if points.numel() and points.stride(1) != 1:
+            points = points.contiguous()
+        return points, (points.stride(0) if points.shape[0] > 1 else points.shape[1])      # (the stride of a 0- or 1-row tensor is arbitrary)
+
+    def _launch_batched(self, seg, gi, offs, labels, points=None, point_stride=0, x_col=0, angle=0.0, box_args=(None, 0, 0, None, None, None, None),
+                        sem2box=None, score_thr=0.0, ins=None):
+        """`pn_panoptic_points_batched_f32` on the (possibly channel-padded) NHWC logits, read in place; without points and
+        ``box_args`` (``_device_list``): labels only"""
         bsz, ncls, h, w = seg.shape
         assert offs.shape[0] == bsz + 1, "point_offsets must have one entry per sample plus one"
         assert seg.stride(2) == w * seg.stride(3) and (bsz == 1 or seg.stride(0) >= h * w * seg.stride(3))
-        if det is None:
-            hip.call("pn_panoptic_points_batched_f32", seg.data_ptr(), seg.stride(0) if bsz > 1 else 0, bsz, h, w, ncls, seg.stride(3), gi.data_ptr(),
-                     offs.data_ptr(), gi.shape[0], None, 0, 0, 1.0, 0.0, None, 0, 0, None, None, None, None, None, 0.0, labels.data_ptr(), None, hip.stream())
-            return
-        boxes = det["box3d_lidar"]
-        cap = int(boxes.shape[1])
-        point_stride = points.stride(0) if points.shape[0] > 1 else points.shape[1]
         hip.call("pn_panoptic_points_batched_f32", seg.data_ptr(), seg.stride(0) if bsz > 1 else 0, bsz, h, w, ncls, seg.stride(3), gi.data_ptr(),
-                 offs.data_ptr(), gi.shape[0], points.data_ptr(), point_stride, x_col, math.cos(angle), math.sin(angle), boxes.data_ptr(), boxes.stride(1), cap,
-                 det["scores"].data_ptr(), det["label_preds"].data_ptr(), det["instances"].data_ptr(), det["count"].data_ptr(), sem2box.data_ptr(),
-                 float(score_thr), labels.data_ptr(), ins.data_ptr(), hip.stream())
+                 offs.data_ptr(), gi.shape[0], hip.ptr(points), point_stride, x_col, math.cos(angle), math.sin(angle), *box_args, hip.ptr(sem2box),
+                 float(score_thr), labels.data_ptr(), hip.ptr(ins), hip.stream())
 
     @torch.no_grad()
     def predict_panoptic_sweep(self, seg_preds, grid_ind, offsets, points, dets, test_cfg, *, voxel_shape, class_names, semantic2box=None,
@@ -401,7 +468,7 @@ class SingleConvHead(nn.Module):
         """``predict_panoptic(device_only=True)`` for ALL sectors of a sweep in ONE launch (`pn_panoptic_points_sweep_f32`), for a detector
         that has every sector's logits and detection list at once (PolarStreamBDCP).  ``seg_preds``: the stacked (nsectors * bs, classes,
         H, W) channels-last logits, sector-major; ``grid_ind`` (rows, 3) int64 / ``offsets`` (nsectors * bs + 1,) int32: the flat rows of
-        ``PolarStreamBDCP._point_rows``; ``points`` (>= rows, F) the stacked point list, one row per ``grid_ind`` row; ``dets``: one
+        ``_flat_rows(example, dev, stacked=True)``; ``points`` (>= rows, F) the stacked point list, one row per ``grid_ind`` row; ``dets``: one
         device list of ``CenterHead.predict(device_only=True)`` under test_cfg.panoptic per sector (their capacities may differ), or None
         for the labels alone (``nsectors`` then says how the stacked batch splits, which matters to dataset order only).  Sector s is rotated by ``predict_panoptic``'s angle (``interval * s``; cuboid: ``2 pi / interval * s``),
         cos / sin taken as ``_launch_batched`` takes them, so the result is bit for bit that of one ``predict_panoptic`` per sector.
@@ -437,44 +504,23 @@ class SingleConvHead(nn.Module):
             assert out_offs.dtype == torch.int32 and out_offs.dim() == 1 and out_offs.is_contiguous() and out_offs.shape[0] == bs + 1, \
                 "out_offsets must be a contiguous int32 (bs + 1,) tensor"
         labels = torch.empty((n_out,), dtype=torch.int64, device=dev)
-        if dets is None:
-            hip.call("pn_panoptic_points_sweep_f32", seg.data_ptr(), seg.stride(0) if total > 1 else 0, nsec, bs, h, w, ncls, seg.stride(3),
-                     grid_ind.data_ptr(), offsets.data_ptr(), rows, None, 0, 0, None, None, 0.0, hip.ptr(dest), hip.ptr(out_offs), n_out, labels.data_ptr(), None,
-                     hip.stream())
-            return labels, None
-        sem2box = self._sem2box(class_names, semantic2box, ncls, dev)
-        x_col = 3 if voxel_shape == "cylinder" else 0
-        hip.require_device(points)
-        assert points.dim() == 2 and points.dtype == torch.float32 and points.shape[1] >= x_col + 2
-        if points.numel() and points.stride(1) != 1:
-            points = points.contiguous()
-        assert rows <= points.shape[0], "valid_grid_ind has more rows than the point list: it must hold one row per point"
-        point_stride = points.stride(0) if points.shape[0] > 1 else points.shape[1]
-        interval = None
-        jobs = (hip.PanopticSectorJob * nsec)()
-        for s, det in enumerate(dets):
-            if not (isinstance(det, dict) and "instances" in det and "count" in det):
-                raise TypeError("predict_panoptic_sweep: every sector's list must be the device list of CenterHead.predict(device_only=True) under test_cfg.panoptic")
-            hip.require_device(*det.values())
-            boxes = det["box3d_lidar"]
-            cap = int(boxes.shape[1])
-            assert boxes.dim() == 3 and boxes.shape[0] == bs and boxes.dtype == torch.float32 and boxes.stride(2) == 1 and boxes.stride(0) == cap * boxes.stride(1)
-            for k, dt in (("scores", torch.float32), ("label_preds", torch.int64), ("instances", torch.int64)):
-                assert tuple(det[k].shape) == (bs, cap) and det[k].dtype == dt and det[k].is_contiguous(), f"the device list's '{k}' must be a contiguous (B, cap) tensor"
-            assert tuple(det["count"].shape) == (bs,) and det["count"].dtype == torch.int32
-            angle = 0.0
-            if s > 0:
-                if interval is None:
-                    interval = float(test_cfg.get("interval") if hasattr(test_cfg, "get") else getattr(test_cfg, "interval"))
-                angle = interval * s if voxel_shape == "cylinder" else 2 * math.pi / interval * s
-            j = jobs[s]
-            j.boxes, j.scores, j.label_preds, j.instances, j.count = (boxes.data_ptr(), det["scores"].data_ptr(), det["label_preds"].data_ptr(),
-                                                                      det["instances"].data_ptr(), det["count"].data_ptr())
-            j.box_stride, j.cap, j.cos_a, j.sin_a = boxes.stride(1), cap, math.cos(angle), math.sin(angle)
-        ins = torch.empty((n_out,), dtype=torch.int64, device=dev)
+        points_ptr, point_stride, x_col, jobs, sem2box, ins = None, 0, 0, None, None, None      # the labels alone
+        if dets is not None:
+            sem2box = self._sem2box(class_names, semantic2box, ncls, dev)
+            x_col = 3 if voxel_shape == "cylinder" else 0
+            points, point_stride = self._point_list(points, x_col)
+            assert rows <= points.shape[0], "valid_grid_ind has more rows than the point list: it must hold one row per point"
+            points_ptr = points.data_ptr()
+            jobs = (hip.PanopticSectorJob * nsec)()
+            for s, det in enumerate(dets):
+                j, angle = jobs[s], self._sector_angle(test_cfg, voxel_shape, s)
+                j.boxes, j.box_stride, j.cap, j.scores, j.label_preds, j.instances, j.count = self._device_list(
+                    det, bs, "predict_panoptic_sweep: every sector's list must be the device list of CenterHead.predict(device_only=True) under test_cfg.panoptic")
+                j.cos_a, j.sin_a = math.cos(angle), math.sin(angle)
+            ins = torch.empty((n_out,), dtype=torch.int64, device=dev)
         hip.call("pn_panoptic_points_sweep_f32", seg.data_ptr(), seg.stride(0) if total > 1 else 0, nsec, bs, h, w, ncls, seg.stride(3), grid_ind.data_ptr(),
-                 offsets.data_ptr(), rows, points.data_ptr(), point_stride, x_col, jobs, sem2box.data_ptr(), float(score_thr), hip.ptr(dest),
-                 hip.ptr(out_offs), n_out, labels.data_ptr(), ins.data_ptr(), hip.stream())
+                 offsets.data_ptr(), rows, points_ptr, point_stride, x_col, jobs, hip.ptr(sem2box), 0.0 if dets is None else float(score_thr), hip.ptr(dest),
+                 hip.ptr(out_offs), n_out, labels.data_ptr(), hip.ptr(ins), hip.stream())
         return labels, ins
 
     def _sem2box(self, class_names, semantic2box, ncls, dev):
@@ -517,38 +563,20 @@ class SingleConvHead(nn.Module):
         bsz, ncls, h, w = seg.shape
         dev = seg.device
         sem2box = self._sem2box(class_names, semantic2box, ncls, dev)
-        sec_id = int(sec_id)
-        angle = 0.0
-        if sec_id > 0:
-            interval = float(test_cfg.get("interval") if hasattr(test_cfg, "get") else getattr(test_cfg, "interval"))
-            angle = interval * sec_id if voxel_shape == "cylinder" else 2 * math.pi / interval * sec_id
+        angle = self._sector_angle(test_cfg, voxel_shape, int(sec_id))
         x_col = 3 if voxel_shape == "cylinder" else 0
-        points = example["points"]
-        hip.require_device(points)
-        assert points.dim() == 2 and points.dtype == torch.float32 and points.shape[1] >= x_col + 2
-        if points.numel() and points.stride(1) != 1:
-            points = points.contiguous()
+        points, point_stride = self._point_list(example["points"], x_col)
         if device_only:
-            det = ret_dict["det"]
-            if not (isinstance(det, dict) and "instances" in det and "count" in det):
-                raise TypeError("predict_panoptic(device_only=True): ret_dict['det'] must be the device list of CenterHead.predict(device_only=True) under test_cfg.panoptic")
-            hip.require_device(*det.values())
+            box_args = self._device_list(ret_dict["det"], bsz, "predict_panoptic(device_only=True): ret_dict['det'] must be the device list of "
+                                         "CenterHead.predict(device_only=True) under test_cfg.panoptic")
             gi, offs = self._flat_rows(example, dev)
             assert gi.shape[0] <= points.shape[0], "valid_grid_ind has more rows than the point list"
-            boxes = det["box3d_lidar"]
-            cap = int(boxes.shape[1])
-            assert boxes.dim() == 3 and boxes.shape[0] == bsz and boxes.dtype == torch.float32 and boxes.stride(2) == 1 and boxes.stride(0) == cap * boxes.stride(1)
-            for k, dt in (("scores", torch.float32), ("label_preds", torch.int64), ("instances", torch.int64)):
-                assert tuple(det[k].shape) == (bsz, cap) and det[k].dtype == dt and det[k].is_contiguous(), f"the device list's '{k}' must be a contiguous (B, cap) tensor"
-            assert tuple(det["count"].shape) == (bsz,) and det["count"].dtype == torch.int32
             labels = torch.empty((gi.shape[0],), dtype=torch.int64, device=dev)
             ins = torch.empty((gi.shape[0],), dtype=torch.int64, device=dev)
-            self._launch_batched(seg, gi, offs, labels, points, x_col, angle, det, sem2box, score_thr, ins)
+            self._launch_batched(seg, gi, offs, labels, points, point_stride, x_col, angle, box_args, sem2box, score_thr, ins)
             ret_dict["seg"], ret_dict["ins"] = labels, ins
             return ret_dict
-        point_stride = points.stride(0) if points.shape[0] > 1 else points.shape[1]      # (the stride of a 0- or 1-row tensor is arbitrary)
-        num = example["num_points"]
-        num = [int(v) for v in (num.tolist() if torch.is_tensor(num) else num)]
+        num = host_counts(example["num_points"])
         assert len(num) == bsz and sum(num) <= points.shape[0], "num_points does not match the batch / the point list"
         dets = ret_dict["det"][0]
         ret_dict["seg"], ret_dict["ins"] = [], []
@@ -576,8 +604,7 @@ class SingleConvHead(nn.Module):
                      box_labels.data_ptr() if m else None, ids.data_ptr() if m else None, m, sem2box.data_ptr(), float(score_thr), labels.data_ptr(),
                      ins.data_ptr(), hip.stream())
             start += n
-            meta = example["metadata"][i]
-            token = meta["token"] if isinstance(meta, dict) and "token" in meta else i
+            token = sample_token(example["metadata"], i)
             ret_dict["seg"].append({token: labels})
             ret_dict["ins"].append({token: ins})
         return ret_dict

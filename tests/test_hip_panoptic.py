@@ -1,10 +1,12 @@
 """GPU parity of the panoptic fusion: `pn_panoptic_points_f32` through SingleConvHead.predict_panoptic against the reference's own
 outputs (tests/golden/panoptic.npz) and the float64 restatement of tests/test_panoptic_host.py on edge shapes; the boxes' instance
-ids through CenterHeadSingle.predict; the PolarStream loop with a segmentation head, with and without test_cfg.panoptic.
+ids through CenterHeadSingle.predict; the per-sample entry against `pn_panoptic_points_batched_f32`, bit for bit; the PolarStream loop with
+a segmentation head, with and without test_cfg.panoptic.
 
 `ins` is compared outside NEAR-TIES: a thing point whose best and second-best float64 distances differ by less than 1e-3 m (f32
 rounding of a distance at 70 m is about 1e-5 m); they may be at most 0.5 % of the thing points, which every comparison asserts."""
 import logging
+import math
 
 import numpy as np
 import pytest
@@ -182,6 +184,82 @@ def test_missing_box_class_is_an_error(dev, head):
     with pytest.raises(ValueError, match="truck"):
         head.predict_panoptic(example, dict(seg_preds=channels_last(logits[None], dev)), {}, dict(det=det), voxel_shape="cylinder",
                               class_names=[[n for n in NAMES if n != "truck"]], sec_id=0)
+
+
+# ------------------------------------------------------------------------------------------------ per-sample entry == batched entry
+PAIR_H = PAIR_W = 16
+PAIR_CLASSES, PAIR_STRIDE, PAIR_CAP, PAIR_ANGLE, PAIR_THR = 5, 8, 1100, 0.7, 0.3
+PAIR_TABLE = [-1, 0, 1, 2, -1, -1]                  # semantic labels 1..3 are things (box labels 0..2), 4 and 5 stuff
+
+
+def draw_pair(points_per_sample, boxes_per_sample, seed=21):
+    """two samples on a 16 x 16 map, 5 classes on a pixel stride of 8 (padding 1e9): every coordinate an integer of [-4, 4], so that box
+    centres repeat and exact distance ties occur; some grid rows outside the map.  The rows past a sample's count hold boxes of the class
+    each point looks for, score 1, exactly on the (rotated) query points, id -777: they must never win.
+    -> the host arrays and (thing points, thing points whose nearest eligible box is not unique) of the drawn data"""
+    r = np.random.default_rng(seed)
+    offs = np.concatenate([[0], np.cumsum(points_per_sample)]).astype(np.int32)
+    ntot = int(offs[-1])
+    logits = np.full((2, PAIR_H, PAIR_W, PAIR_STRIDE), 1e9, np.float32)
+    logits[..., :PAIR_CLASSES] = r.standard_normal((2, PAIR_H, PAIR_W, PAIR_CLASSES)).astype(np.float32)
+    gi = np.stack([np.zeros(ntot, np.int64), r.integers(-1, PAIR_H + 1, ntot), r.integers(0, PAIR_W, ntot)], 1)
+    pts = r.standard_normal((ntot, 7)).astype(np.float32)
+    pts[:, 3:5] = r.integers(-4, 5, (ntot, 2)).astype(np.float32)
+    boxes = r.standard_normal((2, PAIR_CAP, 9)).astype(np.float32)
+    boxes[:, :, :2] = r.integers(-4, 5, (2, PAIR_CAP, 2)).astype(np.float32)
+    scores = r.uniform(0, 1, (2, PAIR_CAP)).astype(np.float32)
+    labels = r.integers(0, 3, (2, PAIR_CAP)).astype(np.int64)
+    ids = r.integers(1, 2 ** 40, (2, PAIR_CAP)).astype(np.int64)
+    # the kernels' f32 arithmetic, operation by operation (no contraction): rotated query points, the class each looks for
+    c, s = np.float32(math.cos(PAIR_ANGLE)), np.float32(math.sin(PAIR_ANGLE))
+    qx, qy = pts[:, 3] * c - pts[:, 4] * s, pts[:, 3] * s + pts[:, 4] * c
+    inside = (gi[:, 1] >= 0) & (gi[:, 1] < PAIR_H)
+    sample = np.repeat(np.arange(2), points_per_sample)
+    lab = np.where(inside, 1 + np.argmax(logits[sample, np.clip(gi[:, 1], 0, PAIR_H - 1), gi[:, 2], :PAIR_CLASSES], -1), 0)
+    want = np.asarray(PAIR_TABLE)[lab]
+    things = ties = 0
+    for b, m in enumerate(boxes_per_sample):
+        rows = np.arange(offs[b], offs[b + 1])
+        for i in rows[want[rows] >= 0]:
+            ok = (scores[b, :m] > np.float32(PAIR_THR)) & (labels[b, :m] == want[i])
+            dx, dy = qx[i] - boxes[b, :m, 0][ok], qy[i] - boxes[b, :m, 1][ok]
+            d = dx * dx + dy * dy
+            things += 1
+            ties += int(d.size > 1 and (d == d.min()).sum() > 1)
+        k = PAIR_CAP - m
+        src = rows[np.arange(k) % len(rows)] if len(rows) else np.zeros(k, np.int64)
+        boxes[b, m:, 0], boxes[b, m:, 1] = (qx[src], qy[src]) if len(rows) else (0.0, 0.0)
+        scores[b, m:], labels[b, m:], ids[b, m:] = 1.0, (np.maximum(want[src], 0) if len(rows) else 0), -777
+    return (logits, gi, pts, offs, boxes, scores, labels, ids), (things, ties)
+
+
+@pytest.mark.parametrize("boxes_per_sample", [(0, 1025), (1, 1024)])
+@pytest.mark.parametrize("points_per_sample", [(0, 257), (1, 256)])
+def test_per_sample_entry_equals_the_batched_entry(dev, points_per_sample, boxes_per_sample):
+    """`pn_panoptic_points_f32` called once per sample == `pn_panoptic_points_batched_f32` on the same buffers, BITWISE on labels and instance
+    ids, under a rotation: point counts below / at / above the 256-lane block, box counts at and one above the 1024-box LDS chunk on lists
+    of capacity 1100, integer coordinates (exact distance ties: the first row wins in both kernels)."""
+    from partner_amd import hip
+    host, (things, ties) = draw_pair(points_per_sample, boxes_per_sample)
+    assert things >= 1 and ties >= 1, "the drawn data holds no thing-labelled point or no exact distance tie"
+    logits, gi, pts, offs, boxes, scores, labels, ids = (torch.from_numpy(a).to(dev) for a in host)
+    count = torch.tensor(boxes_per_sample, dtype=torch.int32, device=dev)
+    sem = torch.tensor(PAIR_TABLE, dtype=torch.int32, device=dev)
+    ntot = int(offs[-1])
+    c, s = math.cos(PAIR_ANGLE), math.sin(PAIR_ANGLE)
+    seg, ins, one_seg, one_ins = (torch.full((ntot,), -5, dtype=torch.int64, device=dev) for _ in range(4))
+    hip.call("pn_panoptic_points_batched_f32", logits.data_ptr(), PAIR_H * PAIR_W * PAIR_STRIDE, 2, PAIR_H, PAIR_W, PAIR_CLASSES, PAIR_STRIDE, gi.data_ptr(),
+             offs.data_ptr(), ntot, pts.data_ptr(), 7, 3, c, s, boxes.data_ptr(), 9, PAIR_CAP, scores.data_ptr(), labels.data_ptr(), ids.data_ptr(),
+             count.data_ptr(), sem.data_ptr(), PAIR_THR, seg.data_ptr(), ins.data_ptr(), hip.stream())
+    for b, (n, m) in enumerate(zip(points_per_sample, boxes_per_sample)):
+        lo = int(host[3][b])
+        hip.call("pn_panoptic_points_f32", logits[b].data_ptr(), PAIR_H, PAIR_W, PAIR_CLASSES, PAIR_STRIDE, gi[lo:].data_ptr(), n, pts[lo:].data_ptr(), 7, 3, c, s,
+                 boxes[b].data_ptr(), 9, scores[b].data_ptr(), labels[b].data_ptr(), ids[b].data_ptr(), m, sem.data_ptr(), PAIR_THR, one_seg[lo:].data_ptr(),
+                 one_ins[lo:].data_ptr(), hip.stream())
+    torch.cuda.synchronize()
+    assert torch.equal(one_seg, seg) and torch.equal(one_ins, ins)
+    assert not bool((ins == -777).any()) and not bool((ins == -5).any()) and not bool((seg == -5).any()), "a row past count won, or a point row was not written"
+    assert int((ins > 0).sum()) >= 1 and int((seg == 0).sum()) >= 1, "no point took an instance id, or no row outside the map"
 
 
 # ------------------------------------------------------------------------------------------------ the streamed detector
