@@ -422,6 +422,26 @@ size_t pn_channel_sum_workspace_bytes(int c);
 int pn_channel_sum_f32(const float *x, long long pixels, int pixel_stride, int channel_offset, int c,
                        float *out, int accumulate, void *workspace, size_t workspace_bytes,
                        pn_stream_t stream);
+/* Data gradient of the CONTEXT ROWS of a context-padded 3x3 convolution: autograd through the torch.cat / F.pad of
+ * ConvBDCP.forward (rpn_context.py:112-162; ConvContext.forward 30-44) when the sector-streaming necks train.  The layer computes
+ * conv3x3(P), P = [top (1 row); x (in_h rows); bottom (1 row)], no padding along H, padding 1 along W, stride 1 or 2.  The gradient of
+ * P's centre rows is the data gradient of the plain pad-1 convolution (above / below: pn_conv2d_nhwc_f32 on dout); this entry gives
+ *   d_top[b, x, ci]    = sum_{kw, co} w[co, ci, 0, kw] * dout[b, 0,      (x + 1 - kw) / stride, co]
+ *   d_bottom[b, x, ci] = sum_{kw, co} w[co, ci, 2, kw] * dout[b, oh - 1, (x + 1 - kw) / stride, co]
+ * (terms with a fractional or out-of-range column dropped) in ONE launch on the fp32 matrix instructions, reading the forward weight
+ * (Cout, Cin, 3, 3) as it is.  dout: NHWC (batch, oh, ow, dout_pixel_stride) with the layer's channels at dout_channel_offset;
+ * oh = (in_h - 1) / stride + 1, ow = (in_w - 1) / stride + 1.  Each border is written -- *_accumulate != 0: added -- at
+ * dst[b * sample_stride + x * pixel_stride + channel_offset + ci] (strides in floats), i.e. into any row of any NHWC map; either
+ * pointer may be null (that border is skipped), not both.  When (in_h - 1) % stride != 0 the forward never read the bottom row:
+ * d_bottom is zero (written as zeros, or left alone when accumulating).  Deterministic: fixed summation order (kw, then co), one
+ * lane per result, no float atomics.  PN_ERR_INVALID without a launch: kernel != 3x3, stride not 1 or 2, cin or cout not a multiple
+ * of 4, null weight / dout, dout not 16-byte aligned or its strides / offsets not multiples of 4, a destination that is not
+ * 16-byte aligned with strides / offset multiples of 4 and pixel_stride >= channel_offset + cin, both borders on the same row. */
+int pn_conv_border_dgrad_f32(const float *w_oihw, int cout, int cin, int kh, int kw, int stride, const float *dout, int batch,
+                             int oh, int ow, int dout_pixel_stride, int dout_channel_offset, int in_h, int in_w, float *d_top,
+                             long long top_sample_stride, int top_pixel_stride, int top_channel_offset, int top_accumulate,
+                             float *d_bottom, long long bottom_sample_stride, int bottom_pixel_stride, int bottom_channel_offset,
+                             int bottom_accumulate, pn_stream_t stream);
 /* Data gradient = pn_conv2d_nhwc_f32 on dout with re-packed weights:
  *   stride 1:  pack with pn_pack_conv_dgrad_weight_f32 (taps mirrored, Cin/Cout swapped;
  *              pn_conv_packed_weight_floats(cin, cout, kh, kw, 1) floats), run a kh x kw

@@ -528,10 +528,10 @@ class PolarStreamBDCP(PolarStream):
         return torch.cat(outs, 0)
 
     def _refuse_unbuilt(self, return_loss):
+        """``forward`` runs the folded eval-mode kernels; with ``return_loss`` it returns the loss of those predictions.  Training -- batch
+        statistics and gradients -- is ``train_stream.PolarStreamBDCPTrainStep``."""
         eval_only(self, "PolarStreamBDCP")
-        if return_loss:
-            raise NotImplementedError("PolarStreamBDCP: training (the two-sweep loss path) is not built")
-        if self._test_flag("panoptic") and self.seg_head is None:
+        if not return_loss and self._test_flag("panoptic") and self.seg_head is None:
             raise NotImplementedError("PolarStreamBDCP: test_cfg.panoptic (polarstream.py:423-460) needs a seg head -- the panoptic fusion assigns the "
                                       "boxes' instance ids to the seg head's per-point labels")
 
@@ -559,6 +559,11 @@ class PolarStreamBDCP(PolarStream):
             return self.warp_prev_sweep(cur, torch.as_tensor(example["transform_matrix"])[:bs], bs)
         x2 = self._stream_sectors(canvas, kwargs["prev_sweep"], bs, mode)
         preds = self._heads(canvas, x2)             # polarstream.py:404-408: the seg head (when there is one) on the stacked canvases + neck output
+        if return_loss:                             # polarstream.py:409-416: both super-tasks' terms on the STACKED predictions, one dict
+            losses = self.bbox_head.loss(example, preds)
+            if self.seg_head is not None:
+                losses.update(self.seg_head.loss(example, preds))
+            return losses
         if kwargs.get("raw_preds", False) or self.test_cfg is None:
             return [self._sector(preds, example, i, bs)[0] for i in range(nsec)]
         stateful, panoptic = bool(self._get("stateful_nms", False)), self._test_flag("panoptic")
@@ -716,6 +721,8 @@ class PolarStreamBDCP(PolarStream):
             return self._forward_device(example, **kwargs)
         prev_sweep = self.forward_one_sweep(example[0], "feature_only", False, **kwargs)
         rets = self.forward_one_sweep(example[1], "train" if return_loss else "eval", return_loss, prev_sweep=prev_sweep, **kwargs)
+        if return_loss:
+            return rets
         ex = example[1]
         bs = len(ex["num_points"]) // self.nsectors
         stateful = self.test_cfg is not None and (bool(self._get("stateful_nms", False)) or self._test_flag("panoptic"))

@@ -49,6 +49,26 @@ def conv_wgrad(x: torch.Tensor, dout: torch.Tensor, kh: int, kw: int, stride=1, 
     return out
 
 
+def conv_border_dgrad(weight: torch.Tensor, dout: torch.Tensor, stride: int, in_h: int, in_w: int, top=None, bottom=None,
+                      dout_channel_offset=0) -> None:
+    """gradients of the two CONTEXT rows of a context-padded 3x3 convolution (``pn_conv_border_dgrad_f32``; the centre rows are
+    ``ConvDgrad(weight, stride, 1)``).  weight (Cout, Cin, 3, 3) as the forward holds it; dout NHWC (B, OH, OW, Ct) of the convolution of
+    the (in_h + 2, in_w) padded map.  ``top`` / ``bottom``: None or ``(map, row, channel_offset, accumulate)`` -- the border's gradient
+    (B, in_w, Cin) is written (accumulate: added) into row ``row`` of the NHWC ``map`` (B, rows, in_w, C) at that channel offset."""
+    hip.require_device(weight, dout, None if top is None else top[0], None if bottom is None else bottom[0])
+    assert weight.dim() == 4 and weight.is_contiguous() and dout.dim() == 4 and dout.is_contiguous()
+    cout, cin, kh, kw = weight.shape
+    b, oh, ow, ct = dout.shape
+
+    def dst(t):
+        if t is None:
+            return (None, 0, 0, 0, 0)
+        m, row, co, acc = t
+        assert m.dim() == 4 and m.is_contiguous() and m.shape[0] == b and m.shape[2] == in_w and 0 <= row < m.shape[1], (m.shape, row)
+        return (m.data_ptr() + 4 * row * m.stride(1), m.stride(0), m.stride(2), int(co), int(bool(acc)))
+
+    hip.call("pn_conv_border_dgrad_f32", weight.data_ptr(), cout, cin, kh, kw, int(stride), dout.data_ptr(), b, oh, ow, ct,
+             int(dout_channel_offset), int(in_h), int(in_w), *dst(top), *dst(bottom), hip.stream())
 
 
 

@@ -201,12 +201,14 @@ class _Conv:
             return ops.conv_chain([self.layer], x)
         return self.layer(x, out=out, out_channel_offset=out_co, in_channel_offset=in_co)
 
-    def bwd(self, dout, cout: Optional[int] = None, need_dx=True, dx=None, dx_co=0, accumulate=False):
-        """dout: NHWC gradient of the (pre-activation) output, own tensor (channel offset 0)"""
+    def bwd(self, dout, cout: Optional[int] = None, need_dx=True, dx=None, dx_co=0, accumulate=False, wacc=False):
+        """dout: NHWC gradient of the (pre-activation) output, own tensor (channel offset 0).  ``wacc``: ADD the parameter gradients (a layer
+        called several times per iteration: the sector calls of the streaming necks)"""
         w = self.ps.p[self.wname]
         gw = self.ps.g[self.wname]
         if self.transposed:
-            self.ps.side.run(lambda: ops.conv_wgrad(dout, self.x, 2, 2, 2, 0, cout=w.shape[0], dout_channel_offset=self.in_co, out=gw), dout, self.x)
+            self.ps.side.run(lambda: ops.conv_wgrad(dout, self.x, 2, 2, 2, 0, cout=w.shape[0], dout_channel_offset=self.in_co, out=gw, accumulate=wacc),
+                             dout, self.x)
             if need_dx:
                 self.dgrad.repack(w, token=self.ps.fresh)
                 return self.dgrad(dout, out=dx, out_channel_offset=dx_co, accumulate=accumulate)
@@ -215,9 +217,9 @@ class _Conv:
 
         def weight_grads():
             ops.conv_wgrad(self.x, dout, self.k, self.k, self.stride, self.pad, cin=self.cin_real, in_channel_offset=self.in_co,
-                           cout=cout, out=gw)
+                           cout=cout, out=gw, accumulate=wacc)
             if self.bname is not None:
-                ops.channel_sum(dout, c=cout, out=self.ps.g[self.bname])
+                ops.channel_sum(dout, c=cout, out=self.ps.g[self.bname], accumulate=wacc)
 
         self.ps.side.run(weight_grads, dout, self.x)
         if need_dx:
@@ -250,8 +252,9 @@ class _PillarConv:
         self.tables = self.layer.build_tables(self.vi, x.shape[0], x.shape[1], x.shape[2])
         return self.layer.forward_tables(x, self.vi, self.tables)
 
-    def bwd(self, dout, cout=None, need_dx=True, dx=None, dx_co=0, accumulate=False):
+    def bwd(self, dout, cout=None, need_dx=True, dx=None, dx_co=0, accumulate=False, wacc=False):
         """-> d(pillar features) (n_cap, Cin) instead of a dense canvas gradient (dynamic_pfn_bwd takes either)"""
+        assert not wacc, "the pillar-rows first layer is called once per iteration"
         self.ps.side.run(lambda: self.layer.wgrad(self.x, dout, self.vi, self.tables, out=self.ps.g[self.wname]), dout, self.x, self.tables)
         return self.layer.dgrad_features(dout, self.vi, self.tables) if need_dx else None
 
@@ -273,13 +276,13 @@ class _ConvBNReLU:
                                              self.bn.running_mean, self.bn.running_var, act=RELU, out=out, out_channel_offset=out_co)
         return res
 
-    def bwd(self, dout, dout_co=0, need_dx=True, dx=None, accumulate=False):
+    def bwd(self, dout, dout_co=0, need_dx=True, dx=None, accumulate=False, wacc=False):
         c = self.y.shape[3]
         inplace = dout.shape[3] == c and dout_co == 0
         dy = dout if inplace else torch.empty_like(self.y)
         ops.batchnorm_bwd(self.y, dout, self.ps.p[self.gname], self.ps.p[self.bname], self.stat, act=RELU, dx=dy,
-                          dgamma=self.ps.g[self.gname], dbeta=self.ps.g[self.bname], dout_channel_offset=dout_co)
-        return self.conv.bwd(dy, need_dx=need_dx, dx=dx, accumulate=accumulate)
+                          dgamma=self.ps.g[self.gname], dbeta=self.ps.g[self.bname], dout_channel_offset=dout_co, accumulate=wacc)
+        return self.conv.bwd(dy, need_dx=need_dx, dx=dx, accumulate=accumulate, wacc=wacc)
 
 
 class _ConvReLU:
@@ -467,7 +470,11 @@ class PolarPillarTrainStep:
         self.reader, self.neck, self.head = reader, neck, head
         self.spec = ops.GridSpec.from_range(reader.pc_range, reader.voxel_size)
         self.w0, self.w1 = "reader.pfn_layers.0.linear.weight", "reader.pfn_layers.1.linear.weight"
-        # ---- RPN
+        self._build_rpn(neck)
+        self._build_head(head)
+
+    def _build_rpn(self, neck):
+        ps = self.ps
         self.blocks: List[List[_ConvBNReLU]] = []
         for i, blk in enumerate(neck.blocks):
             mods = list(blk._modules.values())
@@ -481,7 +488,9 @@ class PolarPillarTrainStep:
         self.deblocks = [_ConvBNReLU(ps, f"neck.deblocks.{j}.", 0, de[1], de[0]) for j, de in enumerate(neck.deblocks)]
         self.up_start = neck._upsample_start_idx
         self.up_filters = list(neck._num_upsample_filters)
-        # ---- head
+
+    def _build_head(self, head):
+        ps, dev = self.ps, self.dev
         hp = "bbox_head."
         self.code_weights, self.loss_weight = list(head.code_weights), float(head.weight)
         self.ncls = sum(head.num_classes)
@@ -554,14 +563,29 @@ class PolarPillarTrainStep:
                 batch, spec.grid[1], spec.grid[0])
         self.points = points
         canvas = torch.empty((batch, spec.grid[1], spec.grid[0], self.reader.out_channels), dtype=torch.float32, device=self.dev)
-        first = self.blocks[0][0].conv
-        if isinstance(first, _PillarConv):
+        first = self._sparse_first()
+        if first is not None:
             first.vi = self.vi          # only the pillars' cells of the canvas are ever read: no 134 MB-per-sample zero fill
         else:
             hip.call("pn_fill_zero", canvas.data_ptr(), canvas.numel() * 4, hip.stream())
         r = self.reader
         ops.dynamic_pfn(points, self.vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, None, canvas)
         self._prepack()     # issued behind the scatter stage's launches, runs beside them
+        out = self._rpn_forward(canvas, batch)
+        self.x2 = out
+        self.seg_logits = None
+        if self._seg_labels is not None:
+            # the pillar-features first layer builds no dense canvas: the canvas part of the logits is computed on the pillar rows
+            self.seg_logits = self.seg.forward(canvas, out, vi=self.vi if first is not None else None)
+        return self._head_forward(out)
+
+    def _sparse_first(self):
+        """the RPN's first convolution when it runs on the pillar rows (then no dense canvas exists), else None"""
+        first = self.blocks[0][0].conv
+        return first if isinstance(first, _PillarConv) else None
+
+    def _rpn_forward(self, canvas, batch):
+        """canvas (batch, T, R, C) -> the concatenated deblock outputs; keeps what ``_rpn_backward`` needs"""
         x = canvas
         out, off = None, 0
         self.block_out = []
@@ -580,12 +604,10 @@ class PolarPillarTrainStep:
                 de.fwd(x, out=out, out_co=off)
                 off += self.up_filters[j]
         self._packs_ready(1)    # models with a single block reach the head without having met event 1 in the loop
-        self.x2 = out
-        self.seg_logits = None
-        if self._seg_labels is not None:
-            # the pillar-features first layer builds no dense canvas: the canvas part of the logits is computed on the pillar rows
-            self.seg_logits = self.seg.forward(canvas, out, vi=self.vi if isinstance(first, _PillarConv) else None)
-        # ---- head
+        return out
+
+    def _head_forward(self, out):
+        ps = self.ps
         mul = add = None
         if self.has_pos:
             self.cal_mid = {}
@@ -719,7 +741,18 @@ class PolarPillarTrainStep:
             self.seg.backward_x2(seg_dlogits, d_x2)
             self.seg.backward_x1(seg_dlogits, need_dx=False)
         self._bucket_ready(0)   # every head gradient is queued: its exchange overlaps the backward of the RPN
-        # RPN
+        d_block = self._rpn_backward(d_x2)
+        r = self.reader
+        sparse = self._sparse_first() is not None      # then d_block is d(pillar features) (n_cap, C), not a canvas gradient
+        if seg_dlogits is not None:
+            self.seg.backward_canvas(seg_dlogits, d_block)      # the seg head's canvas half: d_canvas, or d_features at the pillar rows
+        ops.dynamic_pfn_bwd(self.points, self.vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset,
+                            d_features=d_block if sparse else None, d_canvas=None if sparse else d_block, dw0=ps.g[self.w0], dw1=ps.g[self.w1])
+        ps.side.join()
+
+    def _rpn_backward(self, d_x2):
+        """gradient of the concatenated deblock outputs -> gradient of the canvas (or of the pillar features); queues the RPN's parameter
+        gradients and declares bucket 1 once the last block's are complete"""
         nblk = len(self.blocks)
         d_block = None
         for i in range(nblk - 1, -1, -1):
@@ -736,13 +769,7 @@ class PolarPillarTrainStep:
             d_block = d
             if i == nblk - 1 and len(self.buckets) > 2:
                 self._bucket_ready(1)
-        r = self.reader
-        sparse = isinstance(self.blocks[0][0].conv, _PillarConv)      # then d_block is d(pillar features) (n_cap, C), not a canvas gradient
-        if seg_dlogits is not None:
-            self.seg.backward_canvas(seg_dlogits, d_block)      # the seg head's canvas half: d_canvas, or d_features at the pillar rows
-        ops.dynamic_pfn_bwd(self.points, self.vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset,
-                            d_features=d_block if sparse else None, d_canvas=None if sparse else d_block, dw0=ps.g[self.w0], dw1=ps.g[self.w1])
-        ps.side.join()
+        return d_block
 
     def _bucket_ready(self, k: int) -> None:
         """start the SUM all-reduce of gradient bucket k (asynchronous: RCCL's stream waits for the kernels queued so far and
@@ -802,6 +829,11 @@ class PolarPillarTrainStep:
         step builds the targets itself from its voxel index (``ops.voxel_labels_from_points``: the dataset's majority vote on the device) and
         trains exactly as with the ``voxel_labels`` that vote gives.  Both: ValueError.  Neither (or a model without a seg head): the
         det-only step; a seg head's gradients are then zero."""
+        return self._forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale, voxel_labels, seg_loss_scale, point_labels)
+
+    def _forward_backward(self, points, sample_offsets, batch, targets, grid_ind=None, grad_scale=1.0, voxel_labels=None, seg_loss_scale=1.0,
+                          point_labels=None):
+        """the body of ``forward_backward`` (what ``step`` runs: a subclass may give ``forward_backward`` another argument list)"""
         seg_scale = seg_loss_scale_value(seg_loss_scale)
         self._seg_labels = self._point_labels = self.seg_loss = None
         if voxel_labels is not None and point_labels is not None:
@@ -905,8 +937,8 @@ class PolarPillarTrainStep:
             self._bufsync.sync(force=force)
         # the reference averages the gradients over ranks (dist_utils.py:17-28): fold 1/world into the loss gradient
         try:
-            loss = self.forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world, voxel_labels=voxel_labels,
-                                         seg_loss_scale=seg_loss_scale, point_labels=point_labels)
+            loss = self._forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world, voxel_labels=voxel_labels,
+                                          seg_loss_scale=seg_loss_scale, point_labels=point_labels)
             if self._exchange is not None:
                 self._exchange.finish()   # the last bucket (reader + first blocks), then the stream waits for all of them
         finally:
