@@ -13,26 +13,27 @@ CenterHeadSinglePos  and one fused clip + decoupled-weight-decay + Adam update o
 parameter buffer.  All arithmetic runs in kernels of libpartner_hip; PyTorch allocates tensors and
 (for world_size > 1) all-reduces the flat gradient buffer through torch.distributed (RCCL).
 
+The step is made of parts: ``ParamStore`` (the flat buffers), a neck part (``RpnTrain`` here, ``train_stream.ContextNeckTrain``), the head
+part (``train_head.CenterHeadTrain``), the seg head (``seg_heads.SegHeadTrain``) and ``FlatAdam`` (schedule, clip, Adam, checkpoint); the
+layer wrappers they are built from are in ``train_layers``.
+
 The module's parameters are re-bound to views of the flat buffer, so ``state_dict()`` keeps the
 reference's keys and the inference path (after ``PlanCache`` invalidation) sees the trained weights.
 """
 from __future__ import annotations
 
 import math
-import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Sequence, Tuple
 
-import numpy as np
 import torch
 from torch import nn
 
 from . import hip, ops
 from .routes import R
-from .heads import CenterHeadSingle, CenterHeadSinglePos, RangeStratified
-from .nn_utils import RSNorm
+from .heads import CenterHeadSingle
 from .readers import DynamicPFNet
-
-RELU, NONE, TANH = ops.ACT_RELU, ops.ACT_NONE, ops.ACT_TANH
+from .train_head import CenterHeadTrain
+from .train_layers import _ConvBNReLU, _PillarConv      # (_PillarConv: tests import it from here)
 
 
 def one_cycle(step: int, total_step: int, lr_max: float, moms: Sequence[float], div_factor: float, pct_start: float):
@@ -49,9 +50,6 @@ def one_cycle(step: int, total_step: int, lr_max: float, moms: Sequence[float], 
         return cos(lr_max, low / 1e4, pct), cos(moms[1], moms[0], pct)
     pct = step / a1
     return cos(low, lr_max, pct), cos(moms[0], moms[1], pct)
-
-
-_SideStream = ops.SideStream
 
 
 def seg_loss_scale_value(seg_loss_decay) -> float:
@@ -88,7 +86,7 @@ class ParamStore:
         self.flat_g = torch.zeros(off, dtype=torch.float32, device=device)
         self.flat_m = torch.zeros(off, dtype=torch.float32, device=device)
         self.flat_v = torch.zeros(off, dtype=torch.float32, device=device)
-        self.side = _SideStream(device)
+        self.side = ops.SideStream(device)
         self.fresh = None            # token of the iteration whose packed weights were refreshed ahead (PolarPillarTrainStep._prepack)
         self.convs: List[object] = []   # the step's convolution wrappers (prepack_fwd / prepack_bwd), in construction order
         self.p: Dict[str, torch.Tensor] = {}
@@ -148,285 +146,153 @@ def load_optimizer_state(ps: ParamStore, state: Dict[str, object]) -> int:
     return int(state["iter"])
 
 
-# F(4, 3) in the training FORWARD only on maps of at most this many pixels (the 128 x 128 and 64 x 64 layers): with it on the 256 x 256
-# layers too the full-size gradient test misses its 2e-2 bound on the 95th percentile (2.2e-2: the forward's rounding is amplified
-# through the batch statistics); the data gradients take F(4, 3) everywhere (ops.ConvDgrad)
-# forward of the 3x3 / stride-1 layers on maps up to this size on the chained F(2,3) x F(4,3) kernel (NHWC -> planes + one launch: 77 against
-# 91 us on the 64 x 64 x 256 layers at batch 4, -0.05 ms per iteration; the gradient statistics of the full-size test do not move; the
-# same kernel as the data gradient measured no gain beside the weight gradients and is not used)
+class FlatAdam:
+    """The optimizer of every training step: OneCycle schedule, gradient-norm clip, decoupled weight decay and Adam in one fused update over
+    the flat buffers of a ``ParamStore``; checkpoint / resume of its state (the reference saves model + optimizer state per epoch,
+    det3d/torchie/trainer/trainer.py:342-372) and the broadcast of the initial parameters."""
+
+    def __init__(self, ps: ParamStore, model: nn.Module, total_steps: int, lr_max, moms, div_factor, pct_start, weight_decay, max_norm, beta2, eps):
+        self.ps, self.model = ps, model
+        self.sched = dict(total=total_steps, lr_max=lr_max, moms=tuple(moms), div=div_factor, pct=pct_start)
+        self.wd, self.max_norm, self.beta2, self.eps = weight_decay, max_norm, beta2, eps
+        self.iter = 0
+
+    def step(self):
+        s, ps = self.sched, self.ps
+        lr, beta1 = one_cycle(self.iter, s["total"], s["lr_max"], s["moms"], s["div"], s["pct"])
+        total_norm = ops.grad_norm(ps.flat_g)
+        ops.adam_step(ps.flat_p, ps.flat_g, ps.flat_m, ps.flat_v, self.iter + 1, lr, beta1, self.beta2, self.eps,
+                      self.wd, total_norm=total_norm, max_norm=self.max_norm)
+        self.iter += 1
+        invalidate_inference_plans(self.model)   # the kernels updated the parameters behind the plans' packed copies (f32 and bf16)
+        return total_norm
+
+    def state_dict(self) -> Dict[str, object]:
+        """optimizer-side state; the parameters themselves are in ``model.state_dict()`` (views of the flat buffer)"""
+        return optimizer_state(self.ps, self.iter, self.sched)
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.iter = load_optimizer_state(self.ps, state)
+        self.sched.update(state.get("schedule", {}))
+        invalidate_inference_plans(self.model)
+
+    def sync_initial_params(self, force=False):
+        """rank 0's parameters (and floating-point buffers: BatchNorm running statistics) to every rank, once before the first step
+        -- what DistributedDataParallel's constructor does in the reference (det3d/torchie/apis/train.py:330-336)"""
+        from .dist_utils import broadcast_flat_params
+        broadcast_flat_params(self.ps.flat_p, force=force)
+        for b in self.model.buffers():
+            if b.dtype.is_floating_point:
+                broadcast_flat_params(b, force=force)
 
 
-class _Conv:
-    """plain convolution (optional bias, optional fused activation) with explicit backward"""
+class OptimizerForwards:
+    """the optimizer's surface on a step object (``self.opt``: a FlatAdam)"""
+    iter = property(lambda self: self.opt.iter)
+    sched = property(lambda self: self.opt.sched)
 
-    def __init__(self, ps: ParamStore, wname: str, bname: Optional[str], stride=1, pad=0, act=NONE, transposed=False,
-                 cin_pad: Optional[int] = None):
-        self.ps, self.wname, self.bname = ps, wname, bname
-        w = ps.p[wname]
-        self.stride, self.pad, self.act, self.transposed = stride, pad, act, transposed
-        self.k = w.shape[2]
-        if transposed:  # ConvTranspose2d(k=2, s=2): weight (Cin, Cout, 2, 2)
-            self.layer = ops.ConvLayer(w, deconv2x2=True, act=act)
-            # its data gradient is the stride-2 convolution with the same tensor read as (Cout_conv, Cin_conv, 2, 2)
-            self.dgrad = ops.ConvLayer(w, stride=2, pad=0)
-        else:
-            self.layer = ops.ConvLayer(w, stride=stride, pad=pad, shift=None if bname is None else ps.p[bname], act=act, wino4=R.train_wino4_max_pixels > 0)
-            self.layer.wino4_max_pixels = R.train_wino4_max_pixels
-            if cin_pad is not None:
-                self.layer.pad_input_channels(cin_pad)
-            self.dgrad = ops.ConvDgrad(w, stride, pad)
-        self.cin_real = w.shape[1] if not transposed else w.shape[0]
-        self.x = None
-        self.in_co = 0
-        ps.convs.append(self)
+    def optimizer_step(self):
+        return self.opt.step()
 
-    def prepack_fwd(self, token):
-        self.layer.repack(self.ps.p[self.wname], None if self.bname is None else self.ps.p[self.bname], token=token)
-        self.layer.prepack_used()
+    def state_dict(self) -> Dict[str, object]:
+        return self.opt.state_dict()
 
-    def prepack_bwd(self, token):
-        self.dgrad.repack(self.ps.p[self.wname], token=token)
-        self.dgrad.prepack_used()
-
-    def _chain_ok(self, t, layer) -> bool:
-        return (R.train_chain_max_pixels > 0 and not self.transposed and self.k == 3 and self.stride == 1 and self.pad == 1
-                and t.shape[1] * t.shape[2] <= R.train_chain_max_pixels and t.shape[3] == layer.cin
-                and ops.conv_chain_supported([layer], t.shape[0], t.shape[1], t.shape[2]))
-
-    def fwd(self, x, out=None, out_co=0, in_co=0):
-        w = self.ps.p[self.wname]
-        self.layer.repack(w, None if self.bname is None else self.ps.p[self.bname], token=self.ps.fresh)
-        self.x, self.in_co = x, in_co
-        if out is None and in_co == 0 and self._chain_ok(x, self.layer):
-            return ops.conv_chain([self.layer], x)
-        return self.layer(x, out=out, out_channel_offset=out_co, in_channel_offset=in_co)
-
-    def bwd(self, dout, cout: Optional[int] = None, need_dx=True, dx=None, dx_co=0, accumulate=False, wacc=False):
-        """dout: NHWC gradient of the (pre-activation) output, own tensor (channel offset 0).  ``wacc``: ADD the parameter gradients (a layer
-        called several times per iteration: the sector calls of the streaming necks)"""
-        w = self.ps.p[self.wname]
-        gw = self.ps.g[self.wname]
-        if self.transposed:
-            self.ps.side.run(lambda: ops.conv_wgrad(dout, self.x, 2, 2, 2, 0, cout=w.shape[0], dout_channel_offset=self.in_co, out=gw, accumulate=wacc),
-                             dout, self.x)
-            if need_dx:
-                self.dgrad.repack(w, token=self.ps.fresh)
-                return self.dgrad(dout, out=dx, out_channel_offset=dx_co, accumulate=accumulate)
-            return None
-        cout = w.shape[0] if cout is None else cout
-
-        def weight_grads():
-            ops.conv_wgrad(self.x, dout, self.k, self.k, self.stride, self.pad, cin=self.cin_real, in_channel_offset=self.in_co,
-                           cout=cout, out=gw, accumulate=wacc)
-            if self.bname is not None:
-                ops.channel_sum(dout, c=cout, out=self.ps.g[self.bname], accumulate=wacc)
-
-        self.ps.side.run(weight_grads, dout, self.x)
-        if need_dx:
-            self.dgrad.repack(w, token=self.ps.fresh)
-            return self.dgrad(dout, out=dx, out_channel_offset=dx_co, accumulate=accumulate)
-        return None
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.opt.load_state_dict(state)
 
 
-class _PillarConv:
-    """the first convolution of the RPN on the sparse pillar canvas (ops.PillarConvLayer, csrc/pillar_conv.hip): forward over the
-    (pillar, tap) pairs, data gradient straight to d(pillar features), weight gradient over the pairs -- the dense forms spend
-    2.2 ms of a bs = 4 iteration on a map that is 89 % zeros.  ``vi`` (the iteration's VoxelIndex) is set before ``fwd``."""
+class RpnTrain:
+    """The RPN (det3d/models/necks/rpn.py:144-159) in training form over a ``ParamStore``: a neck part of the step.
+      ``forward(canvas, nsectors, **sweep)`` -> the concatenated deblock outputs (this neck: one sector, no sweep arguments)
+      ``backward(d_x2, block_done)``       -> the gradient of the canvas, or of the pillar features with a ``sparse_first`` layer;
+                                              ``block_done(i)`` once the parameter gradients of block i (and its deblock) are queued
+      ``sparse_first``                     the first convolution when it runs on the pillar rows (then no dense canvas exists), else None
+      ``early_convs()``                    the wrappers whose forward layouts the main stream takes before it waits for pack event 1
+      ``block_out``                        the blocks' outputs of the last forward
+    ``wait_packs(k)``: the step's wait for pack event k (PolarPillarTrainStep._prepack)."""
 
-    def __init__(self, ps: ParamStore, wname: str, stride: int):
-        self.ps, self.wname = ps, wname
-        self.layer = ops.PillarConvLayer(ps.p[wname], stride)
-        self.vi = self.x = self.tables = None
-        ps.convs.append(self)
+    def __init__(self, ps: ParamStore, neck: nn.Module, wait_packs=lambda k: None):
+        self.wait_packs = wait_packs
+        self.blocks: List[List[_ConvBNReLU]] = []
+        self.sparse_first = None
+        for i, blk in enumerate(neck.blocks):
+            mods = list(blk._modules.values())
+            layers = [_ConvBNReLU(ps, f"neck.blocks.{i}.", 1, mods[2], mods[1])]
+            if i == 0 and R.train_pillar_conv and ops.PillarConvLayer.supports(mods[1].weight, mods[1].stride[0], mods[1].groups) and mods[1].out_channels <= 128 \
+                    and mods[1].out_channels in (32, 64, 128):
+                layers[0].conv = self.sparse_first = _PillarConv(ps, f"neck.blocks.{i}.1.weight", mods[1].stride[0])
+            for k in range(4, len(mods), 3):
+                layers.append(_ConvBNReLU(ps, f"neck.blocks.{i}.", k, mods[k + 1], mods[k]))
+            self.blocks.append(layers)
+        self.deblocks = [_ConvBNReLU(ps, f"neck.deblocks.{j}.", 0, de[1], de[0]) for j, de in enumerate(neck.deblocks)]
+        self.up_start = neck._upsample_start_idx
+        self.up_filters = list(neck._num_upsample_filters)
+        self.block_out: List[torch.Tensor] = []
 
-    def prepack_fwd(self, token):
-        self.layer.repack(self.ps.p[self.wname], token=token)
+    def early_convs(self):
+        """block 0 and the deblock fed by block 0"""
+        first = [layer.conv for layer in self.blocks[0]]
+        return first + ([self.deblocks[0].conv] if self.up_start == 0 and self.deblocks else [])
 
-    def prepack_bwd(self, token):
-        pass
+    def forward(self, canvas, nsectors=1):
+        """canvas (batch, T, R, C) -> the concatenated deblock outputs; keeps what ``backward`` needs"""
+        assert nsectors == 1
+        x = canvas
+        out, off = None, 0
+        self.block_out = []
+        for i, layers in enumerate(self.blocks):
+            if i < 2:
+                self.wait_packs(i)
+            for layer in layers:
+                x = layer.fwd(x)
+            self.block_out.append(x)
+            j = i - self.up_start
+            if j >= 0:
+                de = self.deblocks[j]
+                if out is None:
+                    oh, ow = de.conv.layer.out_hw(x.shape[1], x.shape[2])
+                    out = torch.empty((canvas.shape[0], oh, ow, sum(self.up_filters)), dtype=torch.float32, device=canvas.device)
+                de.fwd(x, out=out, out_co=off)
+                off += self.up_filters[j]
+        self.wait_packs(1)    # models with a single block reach the head without having met event 1 in the loop
+        return out
 
-    def fwd(self, x, out=None, out_co=0, in_co=0):
-        assert out is None and in_co == 0
-        self.layer.repack(self.ps.p[self.wname], token=self.ps.fresh)
-        self.x = x
-        self.tables = self.layer.build_tables(self.vi, x.shape[0], x.shape[1], x.shape[2])
-        return self.layer.forward_tables(x, self.vi, self.tables)
-
-    def bwd(self, dout, cout=None, need_dx=True, dx=None, dx_co=0, accumulate=False, wacc=False):
-        """-> d(pillar features) (n_cap, Cin) instead of a dense canvas gradient (dynamic_pfn_bwd takes either)"""
-        assert not wacc, "the pillar-rows first layer is called once per iteration"
-        self.ps.side.run(lambda: self.layer.wgrad(self.x, dout, self.vi, self.tables, out=self.ps.g[self.wname]), dout, self.x, self.tables)
-        return self.layer.dgrad_features(dout, self.vi, self.tables) if need_dx else None
-
-
-class _ConvBNReLU:
-    """Conv2d / ConvTranspose2d (no bias) + BatchNorm2d (batch statistics) + ReLU  (rpn.py:124-142, 80-110)"""
-
-    def __init__(self, ps: ParamStore, prefix: str, conv_idx: int, bn: nn.BatchNorm2d, conv: nn.Module):
-        transposed = isinstance(conv, nn.ConvTranspose2d)
-        pad = 1 if conv.kernel_size[0] == 3 else 0  # nn.ZeroPad2d(1) + Conv2d(3, padding=0) == padding 1
-        self.conv = _Conv(ps, f"{prefix}{conv_idx}.weight", None, conv.stride[0], pad, NONE, transposed)
-        self.gname, self.bname = f"{prefix}{conv_idx + 1}.weight", f"{prefix}{conv_idx + 1}.bias"
-        self.ps, self.bn = ps, bn
-        self.y = self.stat = None
-
-    def fwd(self, x, out=None, out_co=0):
-        self.y = self.conv.fwd(x)
-        res, self.stat = ops.batchnorm_train(self.y, self.ps.p[self.gname], self.ps.p[self.bname], self.bn.eps, self.bn.momentum,
-                                             self.bn.running_mean, self.bn.running_var, act=RELU, out=out, out_channel_offset=out_co)
-        return res
-
-    def bwd(self, dout, dout_co=0, need_dx=True, dx=None, accumulate=False, wacc=False):
-        c = self.y.shape[3]
-        inplace = dout.shape[3] == c and dout_co == 0
-        dy = dout if inplace else torch.empty_like(self.y)
-        ops.batchnorm_bwd(self.y, dout, self.ps.p[self.gname], self.ps.p[self.bname], self.stat, act=RELU, dx=dy,
-                          dgamma=self.ps.g[self.gname], dbeta=self.ps.g[self.bname], dout_channel_offset=dout_co, accumulate=wacc)
-        return self.conv.bwd(dy, need_dx=need_dx, dx=dx, accumulate=accumulate, wacc=wacc)
-
-
-class _ConvReLU:
-    """Conv2d(bias) + ReLU of the plain CenterHead (center_head.py:65-109, 166-242)"""
-
-    def __init__(self, ps: ParamStore, wname: str, bname: str, pad: int):
-        self.conv = _Conv(ps, wname, bname, 1, pad, act=RELU)
-        self.z = None
-
-    def fwd(self, x):
-        self.z = self.conv.fwd(x)   # ReLU fused into the epilogue; its output is also the backward mask
-        return self.z
-
-    def bwd(self, dout, dx=None, accumulate=False):
-        dy = ops.relu_bwd(self.z, dout, dx=dout)
-        return self.conv.bwd(dy, dx=dx, accumulate=accumulate)
-
-
-class _ConvGNReLU:
-    """Conv2d(bias) + GroupNorm-family + ReLU (+ calibration second output) of the merged heads"""
-
-    def __init__(self, ps, wname, bname, gname, bename, cgroups, strata, eps, groups=1):
-        self.ps = ps
-        self.groups, self.cgroups, self.strata, self.eps = groups, cgroups, strata, eps
-        self.wname, self.bname, self.gname, self.bename = wname, bname, gname, bename
-        w = ps.p[wname]
-        self.cout = w.shape[0]
-        if groups == 1:
-            self.convs = [_Conv(ps, wname, bname, 1, 1)]
-        else:  # grouped convolution: forward in one launch, backward per group on weight / channel slices
-            self.layer = ops.ConvLayer(w, stride=1, pad=1, groups=groups, shift=ps.p[bname])
-            cg = self.cout // groups
-            self.dgrads = [ops.ConvDgrad(w[g * cg:(g + 1) * cg], 1, 1) for g in range(groups)]
-        self.x = self.y = None
-
-    def fwd(self, x, mul=None, add=None):
-        self.x = x
-        if self.groups == 1:
-            self.y = self.convs[0].fwd(x)
-        else:
-            self.layer.repack(self.ps.p[self.wname], self.ps.p[self.bname])
-            self.y = self.layer(x)
-        self.mul = mul
-        self.stat = torch.empty(2 * self.y.shape[0] * self.strata * self.cgroups, dtype=torch.float32, device=self.y.device)
-        return ops.groupnorm_strat(self.y, self.cgroups, self.strata, self.ps.p[self.gname], self.ps.p[self.bename], self.eps,
-                                   act=RELU, mul=mul, add=add, stat_out=self.stat)
-
-    def bwd(self, dout, dout2=None, dx=None, accumulate=False, need_dx=True):
-        res = ops.groupnorm_strat_bwd(self.y, dout, self.cgroups, self.strata, self.ps.p[self.gname], self.ps.p[self.bename], self.eps,
-                                      RELU, dout2=dout2, mul=self.mul if dout2 is not None else None, dx=dout,
-                                      dgamma=self.ps.g[self.gname], dbeta=self.ps.g[self.bename], stat=self.stat)
-        dy = res[0]
-        extra = res[3:] if dout2 is not None else ()
-        if self.groups == 1:
-            dxr = self.convs[0].bwd(dy, need_dx=need_dx, dx=dx, accumulate=accumulate)
-            return (dxr,) + tuple(extra)
-        w, gw = self.ps.p[self.wname], self.ps.g[self.wname]
-        cg, cin_g = self.cout // self.groups, w.shape[1]
-        def weight_grads():
-            ops.channel_sum(dy, out=self.ps.g[self.bname])
-            for g in range(self.groups):
-                ops.conv_wgrad(self.x, dy, 3, 3, 1, 1, cin=cin_g, in_channel_offset=g * cin_g, cout=cg, dout_channel_offset=g * cg,
-                               out=gw[g * cg:(g + 1) * cg])
-
-        self.ps.side.run(weight_grads, dy, self.x)
-        if dx is None:
-            dx = torch.empty_like(self.x)
-        for g in range(self.groups):
-            self.dgrads[g].repack(w[g * cg:(g + 1) * cg])
-            self.dgrads[g](dy, out=dx, dout_channel_offset=g * cg, out_channel_offset=g * cin_g, accumulate=accumulate)
-        return (dx,) + tuple(extra)
+    def backward(self, d_x2, block_done=None):
+        d_block = None
+        for i in range(len(self.blocks) - 1, -1, -1):
+            j = i - self.up_start
+            if j >= 0:
+                off = sum(self.up_filters[:j])
+                if d_block is None:
+                    d_block = self.deblocks[j].bwd(d_x2, dout_co=off)
+                else:
+                    self.deblocks[j].bwd(d_x2, dout_co=off, dx=d_block, accumulate=True)
+            for layer in reversed(self.blocks[i]):
+                d_block = layer.bwd(d_block)
+            if block_done is not None:
+                block_done(i)
+        return d_block
 
 
-class _StratConvGNReLU:
-    """RangeStratified: per-range-stratum 3x3 convolution + GroupNorm(strata) + ReLU (center_head_parallel.py:27-59)"""
-
-    def __init__(self, ps, prefix: str, m: RangeStratified):
-        self.ps, self.strata, self.nheads = ps, m.ngroups * m.nheads, m.nheads
-        self.wname, self.bname = prefix + "conv.0.weight", prefix + "conv.0.bias"
-        self.gname, self.bename = prefix + "conv.1.weight", prefix + "conv.1.bias"
-        self.eps = m.conv[1].eps
-        w = ps.p[self.wname]
-        self.layer = ops.ConvLayer(w, stride=1, pad=1, range_strata=self.strata, shift=ps.p[self.bname])
-        # r4: gradients at the convolution's own multiply-add count (ops.StratConvDgrad, pn_conv2d_wgrad_f32 with range_strata); r3
-        # expanded dy to strata * C channels and ran ordinary gradient convolutions over the zeros: 1.0 ms of a 14 ms iteration
-        self.masked = not R.train_strat_expand
-        self.dgrad = ops.StratConvDgrad(w, self.strata) if self.masked else ops.ConvDgrad(w, 1, 1)
-        self.x = self.y = None
-        ps.convs.append(self)
-
-    def prepack_fwd(self, token):
-        self.layer.repack(self.ps.p[self.wname], self.ps.p[self.bname], token=token)
-        self.layer.prepack_used()
-
-    def prepack_bwd(self, token):
-        self.dgrad.repack(self.ps.p[self.wname], token=token)
-        self.dgrad.prepack_used()
-
-    def fwd(self, x):
-        self.x = x
-        self.layer.repack(self.ps.p[self.wname], self.ps.p[self.bname], token=self.ps.fresh)
-        self.y = self.layer(x)
-        self.stat = torch.empty(2 * self.y.shape[0] * self.strata * self.nheads, dtype=torch.float32, device=self.y.device)
-        return ops.groupnorm_strat(self.y, self.nheads, self.strata, self.ps.p[self.gname], self.ps.p[self.bename], self.eps, act=RELU,
-                                   stat_out=self.stat)
-
-    def bwd(self, dout, dx, accumulate):
-        dy, _, _ = ops.groupnorm_strat_bwd(self.y, dout, self.nheads, self.strata, self.ps.p[self.gname], self.ps.p[self.bename], self.eps,
-                                           RELU, dx=dout, dgamma=self.ps.g[self.gname], dbeta=self.ps.g[self.bename], stat=self.stat)
-        w = self.ps.p[self.wname]
-        if self.masked:
-            def weight_grads():
-                ops.conv_wgrad(self.x, dy, 3, 3, 1, 1, out=self.ps.g[self.wname], range_strata=self.strata)
-                ops.strat_channel_sum(dy, self.strata, self.ps.g[self.bname])
-
-            self.ps.side.run(weight_grads, dy, self.x)
-            self.dgrad.repack(w, token=self.ps.fresh)
-            return self.dgrad(dy, out=dx, accumulate=accumulate)
-        full = ops.strat_expand(dy, self.strata)  # zeros outside the pixel's stratum: an ordinary conv gradient (the r3 form)
-
-        def weight_grads():
-            ops.conv_wgrad(self.x, full, 3, 3, 1, 1, out=self.ps.g[self.wname])
-            ops.channel_sum(full, out=self.ps.g[self.bname])
-
-        self.ps.side.run(weight_grads, full, self.x)
-        self.dgrad.repack(w, token=self.ps.fresh)
-        return self.dgrad(full, out=dx, accumulate=accumulate)
-
-
-class PolarPillarTrainStep:
+class PolarPillarTrainStep(OptimizerForwards):
     """One training iteration of PointPillars(DynamicPFNet, DynamicPPScatter, RPN, CenterHeadSinglePos).
 
     ``step(points, sample_offsets, batch, targets)`` runs forward (train mode), loss, backward, gradient
     all-reduce (if torch.distributed is initialised with world_size > 1), clip + decoupled wd + Adam with
     the OneCycle schedule, and returns the loss vector [det, hm, loc, num_pos, elem...] (device)."""
 
+    nsec = 1      # sectors per sweep (the streaming step: the model's)
+    # what tests and tools/determinism_check.py read of the neck part under the step's own names
+    blocks = property(lambda self: self.neck_train.blocks)
+    block_out = property(lambda self: self.neck_train.block_out)
+
     def __init__(self, model: nn.Module, total_steps: int, lr_max=0.005, moms=(0.95, 0.85), div_factor=10.0, pct_start=0.4,
-                 weight_decay=0.01, max_norm=35.0, beta2=0.99, eps=1e-8):
+                 weight_decay=0.01, max_norm=35.0, beta2=0.99, eps=1e-8, neck_part=RpnTrain):
         self.model = model
         reader, neck, head = model.reader, model.neck, model.bbox_head
         if not isinstance(reader, DynamicPFNet):
             raise NotImplementedError("training step: the reader must be a DynamicPFNet")
-        self.plain_head = type(head).__name__ == "CenterHead"
-        if not (isinstance(head, CenterHeadSingle) or self.plain_head):
+        if not (isinstance(head, CenterHeadSingle) or type(head).__name__ == "CenterHead"):
             raise NotImplementedError("training step: the head must be CenterHead, CenterHeadSingle or CenterHeadSinglePos")
         reader._check_supported()
         dev = next(model.parameters()).device
@@ -449,8 +315,8 @@ class PolarPillarTrainStep:
         self.ps = ps = ParamStore(model, dev, order_key)
         # gradient buckets [lo, hi) in the order backward completes them: the head, the last RPN block (+ deblock), the rest
         first_head = min((ps.offsets[n][0] for n in ps.names if n.startswith("bbox_head.")), default=ps.total)
-        last_blk = len(neck.blocks) - 1
-        first_last = min((ps.offsets[n][0] for n in ps.names if order_key(n) >= 1 + 2 * last_blk), default=first_head)
+        self.last_block = len(neck.blocks) - 1
+        first_last = min((ps.offsets[n][0] for n in ps.names if order_key(n) >= 1 + 2 * self.last_block), default=first_head)
         self.buckets = [b for b in ((first_head, ps.total), (first_last, first_head), (0, first_last)) if b[1] > b[0]]
         # ---- seg super-task (point_pillars.py:99-103): the head's parameters sort between the RPN and the bbox head (order_key 999), i.e. into
         # the second gradient bucket
@@ -463,313 +329,91 @@ class PolarPillarTrainStep:
             self.seg = SegHeadTrain(seg_head, ps.p["seg_head.conv.weight"], ps.p["seg_head.conv.bias"], ps.g["seg_head.conv.weight"],
                                     ps.g["seg_head.conv.bias"], side=ps.side)
         self._seg_labels = self._point_labels = None
-        self.sched = dict(total=total_steps, lr_max=lr_max, moms=tuple(moms), div=div_factor, pct=pct_start)
-        self.wd, self.max_norm, self.beta2, self.eps = weight_decay, max_norm, beta2, eps
-        self.iter = 0
-        self._exchange = None
-        self.reader, self.neck, self.head = reader, neck, head
+        self.opt = FlatAdam(ps, model, total_steps, lr_max, moms, div_factor, pct_start, weight_decay, max_norm, beta2, eps)
+        self.exchange_enabled = True         # bench.py sets False for its timing-only mode: the same iteration without the collectives (ranks diverge)
+        self.exchange_at_world_1 = False     # tests/test_hip_rccl.py sets True: the collectives run over a ONE-rank group too (dist_utils.init(single_rank_group=True))
+        self.broadcast_buffers = True        # a caller sets False to drop DDP's per-iteration broadcast of rank 0's BatchNorm statistics (dist_utils.BufferSync)
+        self._exchange = self._bufsync = None
+        self._iter_start = torch.cuda.Event()
+        self._pack_ev = [torch.cuda.Event() for _ in range(3)]
+        self._pack_events = None             # the three events while an iteration's packs run on the side stream
+        self.reader = reader
         self.spec = ops.GridSpec.from_range(reader.pc_range, reader.voxel_size)
         self.w0, self.w1 = "reader.pfn_layers.0.linear.weight", "reader.pfn_layers.1.linear.weight"
-        self._build_rpn(neck)
-        self._build_head(head)
-
-    def _build_rpn(self, neck):
-        ps = self.ps
-        self.blocks: List[List[_ConvBNReLU]] = []
-        for i, blk in enumerate(neck.blocks):
-            mods = list(blk._modules.values())
-            layers = [_ConvBNReLU(ps, f"neck.blocks.{i}.", 1, mods[2], mods[1])]
-            if i == 0 and R.train_pillar_conv and ops.PillarConvLayer.supports(mods[1].weight, mods[1].stride[0], mods[1].groups) and mods[1].out_channels <= 128 \
-                    and mods[1].out_channels in (32, 64, 128):
-                layers[0].conv = _PillarConv(ps, f"neck.blocks.{i}.1.weight", mods[1].stride[0])
-            for k in range(4, len(mods), 3):
-                layers.append(_ConvBNReLU(ps, f"neck.blocks.{i}.", k, mods[k + 1], mods[k]))
-            self.blocks.append(layers)
-        self.deblocks = [_ConvBNReLU(ps, f"neck.deblocks.{j}.", 0, de[1], de[0]) for j, de in enumerate(neck.deblocks)]
-        self.up_start = neck._upsample_start_idx
-        self.up_filters = list(neck._num_upsample_filters)
-
-    def _build_head(self, head):
-        ps, dev = self.ps, self.dev
-        hp = "bbox_head."
-        self.code_weights, self.loss_weight = list(head.code_weights), float(head.weight)
-        self.ncls = sum(head.num_classes)
-        self.has_pos = False
-        if self.plain_head:
-            self.shared = _ConvReLU(ps, hp + "shared_conv.0.weight", hp + "shared_conv.0.bias", 1)
-            # one set of branches per task (center_head.py:166-242: `for task in self.tasks`); r6: any number of tasks -- the branch key is
-            # (task, name), every task has its own loss (center_head.py:250: one term per task, summed by the trainer) and its own targets
-            self.branches = {}
-            self.task_ncls = [int(n) for n in head.num_classes]
-            for t, task in enumerate(head.tasks):
-                for name in task.heads:
-                    convs = [(i, mod) for i, mod in enumerate(getattr(task, name)._modules.values()) if isinstance(mod, nn.Conv2d)]
-                    bp = f"{hp}tasks.{t}.{name}."
-                    hidden = [_ConvReLU(ps, f"{bp}{i}.weight", f"{bp}{i}.bias", mod.padding[0]) for i, mod in convs[:-1]]
-                    i, mod = convs[-1]
-                    self.branches[(t, name)] = ("plain", hidden, _Conv(ps, f"{bp}{i}.weight", f"{bp}{i}.bias", 1, mod.padding[0]), 1)
-            return
-        rs = head.shared_conv[1]
-        assert isinstance(rs, RSNorm)
-        self.shared = _ConvGNReLU(ps, hp + "shared_conv.0.weight", hp + "shared_conv.0.bias", hp + "shared_conv.1.groupnorm.weight",
-                                  hp + "shared_conv.1.groupnorm.bias", rs.num_heads, rs.num_groups, rs.groupnorm.eps)
-        self.branches = {}
-        for name in head.heads:
-            fc = getattr(head, name)
-            mods = list(fc._modules.values())
-            bp = f"{hp}{name}."
-            if isinstance(mods[0], RangeStratified):
-                first = _StratConvGNReLU(ps, bp + "0.", mods[0])
-                last = _Conv(ps, bp + "1.weight", bp + "1.bias", 1, 0)
-                self.branches[name] = ("strat", first, last, 1)
-            else:
-                assert len(mods) == 4, "training step: heads with one hidden conv (num_conv = 2)"
-                groups = mods[0].groups
-                first = _ConvGNReLU(ps, bp + "0.weight", bp + "0.bias", bp + "1.weight", bp + "1.bias", mods[1].num_groups, 1, mods[1].eps,
-                                    groups=groups)
-                w = ps.p[bp + "3.weight"]
-                if groups == 1:
-                    last = _Conv(ps, bp + "3.weight", bp + "3.bias", 1, 1)
-                else:
-                    last = ops.ConvLayer(w, stride=1, pad=1, groups=groups, shift=ps.p[bp + "3.bias"])
-                self.branches[name] = ("conv", first, last, groups)
-        self.has_pos = isinstance(head, CenterHeadSinglePos)
-        if self.has_pos:
-            pos = ops.to_nhwc(head.pos_encoding.to(dev).float())               # (1, A, R, 5)
-            self.pos8 = torch.zeros(pos.shape[:3] + (8,), dtype=torch.float32, device=dev)
-            self.pos8[..., :5] = pos
-            self.cal = {}
-            for kind, last_act in (("calibration_weight", TANH), ("calibration_bias", NONE)):
-                cp = f"{hp}{kind}."
-                self.cal[kind] = (_Conv(ps, cp + "0.weight", cp + "0.bias", 1, 1, act=TANH, cin_pad=8),
-                                  _Conv(ps, cp + "2.weight", cp + "2.bias", 1, 0, act=last_act), last_act)
-        self.code_weights, self.loss_weight = list(head.code_weights), float(head.weight)
-        self.ncls = sum(head.num_classes)
+        self.vi = None
+        self.neck_train = neck_part(ps, neck, self._packs_ready)
+        self.head_train = CenterHeadTrain(ps, head, dev)
 
     # ------------------------------------------------------------------------------------------
-    def _forward(self, points, sample_offsets, batch, grid_ind=None):
-        ps, spec = self.ps, self.spec
+    def _index(self, points, sample_offsets, batch, grid_ind):
+        """-> the VoxelIndex of one sweep (``grid_ind`` given: the dataset's cell indices instead of the device's own)"""
         if grid_ind is None:
-            _, keys = ops.grid_index(points, sample_offsets, batch, spec, want_grid_ind=False)
+            _, keys = ops.grid_index(points, sample_offsets, batch, self.spec, want_grid_ind=False)
             n_dev = sample_offsets[batch:]
         else:
-            keys = ops.keys_from_grid_ind(grid_ind.to(torch.int64).contiguous(), spec, batch)
+            keys = ops.keys_from_grid_ind(grid_ind.to(torch.int64).contiguous(), self.spec, batch)
             n_dev = None
-        self.vi = ops.build_voxel_index(keys, spec, batch, n_dev=n_dev, want_unq=False, sorted_runs=True)
+        return ops.build_voxel_index(keys, self.spec, batch, n_dev=n_dev, want_unq=False, sorted_runs=True)
+
+    def _canvas(self, points, vi, batch, sparse_first=None):
+        """reader + scatter of one sweep.  With the pillar-rows first layer only the pillars' cells of the canvas are ever read: no
+        134 MB-per-sample zero fill"""
+        ps, r, spec = self.ps, self.reader, self.spec
+        canvas = torch.empty((batch, spec.grid[1], spec.grid[0], r.out_channels), dtype=torch.float32, device=self.dev)
+        if sparse_first is not None:
+            sparse_first.vi = vi
+        else:
+            hip.call("pn_fill_zero", canvas.data_ptr(), canvas.numel() * 4, hip.stream())
+        ops.dynamic_pfn(points, vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, None, canvas)
+        return canvas
+
+    def _forward(self, points, sample_offsets, batch, grid_ind, prev_sweep):
+        spec = self.spec
+        self.vi = self._index(points, sample_offsets, batch, grid_ind)
         if self._point_labels is not None:
             # the seg targets from the iteration's own index: per cell the majority of its points' labels, as the loss's int32 label - 1
             # (-1 = ignore) -- no int64 voxel_labels map, no get_labels pass
             self._seg_labels = ops.voxel_labels_from_points(self._point_labels, self.vi, dense=False, loss_labels=True).view(
                 batch, spec.grid[1], spec.grid[0])
         self.points = points
-        canvas = torch.empty((batch, spec.grid[1], spec.grid[0], self.reader.out_channels), dtype=torch.float32, device=self.dev)
-        first = self._sparse_first()
-        if first is not None:
-            first.vi = self.vi          # only the pillars' cells of the canvas are ever read: no 134 MB-per-sample zero fill
-        else:
-            hip.call("pn_fill_zero", canvas.data_ptr(), canvas.numel() * 4, hip.stream())
-        r = self.reader
-        ops.dynamic_pfn(points, self.vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, None, canvas)
+        first = self.neck_train.sparse_first
+        canvas = self._canvas(points, self.vi, batch, first)
         self._prepack()     # issued behind the scatter stage's launches, runs beside them
-        out = self._rpn_forward(canvas, batch)
-        self.x2 = out
+        sweep = {}
+        if prev_sweep is not None:
+            # the previous sweep: reader + scatter with nothing kept (polarstream.py:318-336, under no_grad); the neck warps its maps
+            pv = self._index(prev_sweep["points"], None, batch, prev_sweep["grid_ind"])
+            sweep = dict(prev_canvas=self._canvas(prev_sweep["points"], pv, batch),
+                         warp=lambda inputs: self.model.warp_prev_strips(inputs, prev_sweep["transform_matrix"], batch // self.nsec))
+        x2 = self.neck_train.forward(canvas, self.nsec, **sweep)
         self.seg_logits = None
         if self._seg_labels is not None:
             # the pillar-features first layer builds no dense canvas: the canvas part of the logits is computed on the pillar rows
-            self.seg_logits = self.seg.forward(canvas, out, vi=self.vi if first is not None else None)
-        return self._head_forward(out)
+            self.seg_logits = self.seg.forward(canvas, x2, vi=self.vi if first is not None else None)
+        return self.head_train.forward(x2)
 
-    def _sparse_first(self):
-        """the RPN's first convolution when it runs on the pillar rows (then no dense canvas exists), else None"""
-        first = self.blocks[0][0].conv
-        return first if isinstance(first, _PillarConv) else None
-
-    def _rpn_forward(self, canvas, batch):
-        """canvas (batch, T, R, C) -> the concatenated deblock outputs; keeps what ``_rpn_backward`` needs"""
-        x = canvas
-        out, off = None, 0
-        self.block_out = []
-        for i, layers in enumerate(self.blocks):
-            if i < 2:
-                self._packs_ready(i)
-            for layer in layers:
-                x = layer.fwd(x)
-            self.block_out.append(x)
-            j = i - self.up_start
-            if j >= 0:
-                de = self.deblocks[j]
-                if out is None:
-                    oh, ow = de.conv.layer.out_hw(x.shape[1], x.shape[2])
-                    out = torch.empty((batch, oh, ow, sum(self.up_filters)), dtype=torch.float32, device=self.dev)
-                de.fwd(x, out=out, out_co=off)
-                off += self.up_filters[j]
-        self._packs_ready(1)    # models with a single block reach the head without having met event 1 in the loop
-        return out
-
-    def _head_forward(self, out):
+    def _backward(self, targets, losses, grad_scale: float, seg_dlogits=None):
         ps = self.ps
-        mul = add = None
-        if self.has_pos:
-            self.cal_mid = {}
-            maps = {}
-            for kind, (c0, c1, _) in self.cal.items():
-                mid = c0.fwd(self.pos8)
-                self.cal_mid[kind] = mid
-                maps[kind] = c1.fwd(mid)
-            self.cal_w, self.cal_b = maps["calibration_weight"], maps["calibration_bias"]
-            mul, add = self.cal_w[0], self.cal_b[0]
-        if self.plain_head:
-            xs = x_hm = self.shared.fwd(out)
-        elif mul is not None:
-            xs, x_hm = self.shared.fwd(out, mul=mul, add=add)
-        else:
-            xs = x_hm = self.shared.fwd(out)
-        self.xs, self.x_hm = xs, x_hm
-        preds = {}
-        self.branch_mid = {}
-        self.preds_tasks = None
-        for name, (kind, first, last, groups) in self.branches.items():
-            if kind == "plain":
-                t, nm = name
-                if self.preds_tasks is None:
-                    self.preds_tasks = [dict() for _ in self.task_ncls]
-                z = xs
-                for layer in first:
-                    z = layer.fwd(z)
-                self.preds_tasks[t][nm] = last.fwd(z)
-                continue
-            z = first.fwd(x_hm if name == "hm" else xs)
-            self.branch_mid[name] = z
-            if kind == "conv" and groups > 1:
-                last.repack(ps.p[f"bbox_head.{name}.3.weight"], ps.p[f"bbox_head.{name}.3.bias"])
-                y = last(z)
-            else:
-                y = last.fwd(z)
-            if "_" in name:
-                names = name.split("_")
-                dim = y.shape[3] // len(names)
-                for k, nm in enumerate(names):
-                    preds[nm] = y[..., k * dim:(k + 1) * dim]
-            else:
-                preds[name] = y
-        if self.preds_tasks is not None:
-            preds = self.preds_tasks[0]
-        self.preds = preds
-        return preds
-
-    def _loss_sources(self, preds=None):
-        preds = self.preds if preds is None else preds
-        order = ["reg", "height", "dim"] + (["vel"] if "vel" in preds else []) + ["rot"]
-        return order, [(preds[k], preds[k].shape[3]) for k in order]
-
-    def _task_list(self, targets):
-        """-> [(prediction dict, class count, targets)] per task; a single-task step takes its targets bare, several tasks a list"""
-        if getattr(self, "preds_tasks", None) is None or len(self.preds_tasks) == 1:
-            tg = targets[0] if isinstance(targets, (list, tuple)) else targets
-            return [(self.preds, self.ncls, tg)]
-        assert isinstance(targets, (list, tuple)) and len(targets) == len(self.preds_tasks), "one CenterLossTargets per task"
-        return [(p, n, tg) for p, n, tg in zip(self.preds_tasks, self.task_ncls, targets)]
-
-    # ------------------------------------------------------------------------------------------
-    def _backward(self, targets: ops.CenterLossTargets, loss_out, grad_scale: float, seg_dlogits=None):
-        ps = self.ps
-        tasks = self._task_list(targets)
-        loss_out = loss_out if isinstance(loss_out, (list, tuple)) else [loss_out]
-        multi = len(tasks) > 1
-        d_pred = {}
-        for t, ((preds, ncls, tg), lo) in enumerate(zip(tasks, loss_out)):
-            order, boxes = self._loss_sources(preds)
-            d_hm, d_boxes = ops.center_loss_bwd(preds["hm"], ncls, boxes, tg, self.code_weights, self.loss_weight, lo,
-                                                grad_scale=grad_scale, with_vel="vel" in preds)
-            for nm, d in list(zip(order, d_boxes)) + [("hm", d_hm)]:
-                d_pred[(t, nm) if (multi or self.plain_head) else nm] = d
-        d_xs = torch.empty_like(self.xs)
-        d_xhm = None
-        first_into_xs = True
-        for name, (kind, first, last, groups) in self.branches.items():
-            if kind == "plain":
-                dz = last.bwd(d_pred[name], cout=ps.p[last.wname].shape[0], dx=None if first else d_xs, accumulate=(not first) and not first_into_xs)
-                for li in range(len(first) - 1, -1, -1):
-                    into_xs = li == 0
-                    dz = first[li].bwd(dz, dx=d_xs if into_xs else None, accumulate=into_xs and not first_into_xs)
-                first_into_xs = False
-                continue
-            z = self.branch_mid[name]
-            if kind == "conv" and groups > 1:
-                # grouped final convolution: one output tensor per merged head (e.g. rot | vel)
-                names = name.split("_")
-                w, gw, gb = ps.p[f"bbox_head.{name}.3.weight"], ps.g[f"bbox_head.{name}.3.weight"], ps.g[f"bbox_head.{name}.3.bias"]
-                co, ci = w.shape[0] // groups, w.shape[1]
-                dz = torch.empty_like(z)
-                for g_, nm in enumerate(names):
-                    dy = d_pred[nm]
-                    def weight_grads(dy=dy, g_=g_):
-                        ops.conv_wgrad(z, dy, 3, 3, 1, 1, cin=ci, in_channel_offset=g_ * ci, cout=co, out=gw[g_ * co:(g_ + 1) * co])
-                        ops.channel_sum(dy, c=co, out=gb[g_ * co:(g_ + 1) * co])
-
-                    ps.side.run(weight_grads, dy, z)
-                    ops.ConvDgrad(w[g_ * co:(g_ + 1) * co], 1, 1)(dy, out=dz, out_channel_offset=g_ * ci)
-            else:
-                cout = ps.p[last.wname].shape[0]
-                dz = last.bwd(d_pred[name], cout=cout)
-            if name == "hm" and self.x_hm is not self.xs:
-                d_xhm = first.bwd(dz)[0]
-            elif kind == "strat":
-                first.bwd(dz, dx=d_xs, accumulate=not first_into_xs)
-                first_into_xs = False
-            else:
-                first.bwd(dz, dx=d_xs, accumulate=not first_into_xs)
-                first_into_xs = False
-        # shared conv + RSNorm (+ calibration)
-        if self.plain_head:
-            d_x2 = self.shared.bwd(d_xs)
-        else:
-            res = self.shared.bwd(d_xs, dout2=d_xhm)
-            d_x2 = res[0]
-        if self.has_pos:
-            d_calw, d_calb = res[1], res[2]
-            for kind, dmap, ymap in (("calibration_weight", d_calw, self.cal_w), ("calibration_bias", d_calb, self.cal_b)):
-                c0, c1, last_act = self.cal[kind]
-                d = dmap[None].contiguous()
-                if last_act == TANH:
-                    d = ops.tanh_bwd(ymap, d)
-                dmid = c1.bwd(d)
-                dmid = ops.tanh_bwd(self.cal_mid[kind], dmid, dx=dmid)
-                c0.bwd(dmid, need_dx=False)
+        d_x2 = self.head_train.backward(targets, losses, grad_scale)
         if seg_dlogits is not None:
             # seg head: its RPN half joins d_x2 before the RPN's backward starts; all its parameter gradients (second bucket) are queued here
             self.seg.backward_x2(seg_dlogits, d_x2)
             self.seg.backward_x1(seg_dlogits, need_dx=False)
-        self._bucket_ready(0)   # every head gradient is queued: its exchange overlaps the backward of the RPN
-        d_block = self._rpn_backward(d_x2)
+        self._bucket_ready(0)   # every head gradient is queued: its exchange overlaps the backward of the neck
+
+        def block_done(i):
+            # a bucket is ready only once its gradients are complete (the streaming neck: after sector 0's backward)
+            if i == self.last_block and len(self.buckets) > 2:
+                self._bucket_ready(1)
+
+        d_block = self.neck_train.backward(d_x2, block_done=block_done)
         r = self.reader
-        sparse = self._sparse_first() is not None      # then d_block is d(pillar features) (n_cap, C), not a canvas gradient
+        sparse = self.neck_train.sparse_first is not None      # then d_block is d(pillar features) (n_cap, C), not a canvas gradient
         if seg_dlogits is not None:
             self.seg.backward_canvas(seg_dlogits, d_block)      # the seg head's canvas half: d_canvas, or d_features at the pillar rows
         ops.dynamic_pfn_bwd(self.points, self.vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset,
                             d_features=d_block if sparse else None, d_canvas=None if sparse else d_block, dw0=ps.g[self.w0], dw1=ps.g[self.w1])
         ps.side.join()
-
-    def _rpn_backward(self, d_x2):
-        """gradient of the concatenated deblock outputs -> gradient of the canvas (or of the pillar features); queues the RPN's parameter
-        gradients and declares bucket 1 once the last block's are complete"""
-        nblk = len(self.blocks)
-        d_block = None
-        for i in range(nblk - 1, -1, -1):
-            j = i - self.up_start
-            if j >= 0:
-                off = sum(self.up_filters[:j])
-                if d_block is None:
-                    d_block = self.deblocks[j].bwd(d_x2, dout_co=off)
-                else:
-                    self.deblocks[j].bwd(d_x2, dout_co=off, dx=d_block, accumulate=True)
-            d = d_block
-            for layer in reversed(self.blocks[i]):
-                d = layer.bwd(d)
-            d_block = d
-            if i == nblk - 1 and len(self.buckets) > 2:
-                self._bucket_ready(1)
-        return d_block
 
     def _bucket_ready(self, k: int) -> None:
         """start the SUM all-reduce of gradient bucket k (asynchronous: RCCL's stream waits for the kernels queued so far and
@@ -782,24 +426,17 @@ class PolarPillarTrainStep:
     def _prepack(self):
         """Refresh the packed weight copies of the iteration AHEAD of their use, on the side stream: the forward is a serial chain on the
         main stream with the side stream idle, and every layer's pack launch (2 - 10 us, ~65 per iteration) sat in that chain in front of
-        its convolution.  Three events: the first RPN stage's forward layouts (the main stream meets them after the PFN), the other forward
+        its convolution.  Three events: the first neck stage's forward layouts (the main stream meets them after the PFN), the other forward
         layouts, the data-gradient layouts.  A layout is refreshed here once a call has taken it (the first iteration packs lazily as
         before); ``ps.fresh`` is the iteration's token, the wrappers' own repack calls see it and do nothing."""
         ps = self.ps
-        side = ps.side.stream if R.train_prepack and getattr(self, "_prepack_armed", False) else None   # armed by forward_backward only
-        self._prepack_armed = False
-        self._pack_events = None
-        if side is None:
-            ps.fresh = None
+        if not R.train_prepack or ps.side.stream is None:
+            ps.fresh = self._pack_events = None
             return
         tok = ps.fresh = object()
-        # group 0 = every layout the main stream takes before it waits for event 1: block 0 and the deblock fed by block 0
-        first = {id(layer.conv) for layer in self.blocks[0]}
-        if self.up_start == 0 and self.deblocks:
-            first.add(id(self.deblocks[0].conv))
+        # group 0 = every layout the main stream takes before it waits for event 1
+        first = {id(c) for c in self.neck_train.early_convs()}
         groups = ([c for c in ps.convs if id(c) in first], [c for c in ps.convs if id(c) not in first])
-        if getattr(self, "_pack_ev", None) is None:
-            self._pack_ev = [torch.cuda.Event() for _ in range(3)]
 
         def packs():
             for k, group in enumerate(groups):
@@ -814,11 +451,11 @@ class PolarPillarTrainStep:
         self._pack_events = self._pack_ev
 
     def _packs_ready(self, k: int) -> None:
-        if getattr(self, "_pack_events", None) is not None:
+        if self._pack_events is not None:
             torch.cuda.current_stream().wait_event(self._pack_events[k])
 
     def forward_backward(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, grad_scale=1.0, voxel_labels=None,
-                         seg_loss_scale=1.0, point_labels=None):
+                         seg_loss_scale=1.0, point_labels=None, prev_sweep=None):
         """forward + loss + backward; gradients land in ``self.ps.flat_g`` (overwritten, not accumulated).
 
         ``voxel_labels`` (B,1,H,W) integer on the device, 0 = unlabelled (the dataset's majority vote, preprocess.py:172-191): the seg
@@ -828,12 +465,9 @@ class PolarPillarTrainStep:
         ``point_labels`` (one device uint8 / int32 / int64 label per row of ``points``; < 0: unlabelled) instead of ``voxel_labels``: the
         step builds the targets itself from its voxel index (``ops.voxel_labels_from_points``: the dataset's majority vote on the device) and
         trains exactly as with the ``voxel_labels`` that vote gives.  Both: ValueError.  Neither (or a model without a seg head): the
-        det-only step; a seg head's gradients are then zero."""
-        return self._forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale, voxel_labels, seg_loss_scale, point_labels)
-
-    def _forward_backward(self, points, sample_offsets, batch, targets, grid_ind=None, grad_scale=1.0, voxel_labels=None, seg_loss_scale=1.0,
-                          point_labels=None):
-        """the body of ``forward_backward`` (what ``step`` runs: a subclass may give ``forward_backward`` another argument list)"""
+        det-only step; a seg head's gradients are then zero.
+        ``prev_sweep``: dict(points, grid_ind, transform_matrix) of the previous sweep, for a neck that streams against it
+        (train_stream.PolarStreamBDCPTrainStep)."""
         seg_scale = seg_loss_scale_value(seg_loss_scale)
         self._seg_labels = self._point_labels = self.seg_loss = None
         if voxel_labels is not None and point_labels is not None:
@@ -856,17 +490,10 @@ class PolarPillarTrainStep:
         elif self.seg is not None:
             self.seg.gw.zero_()
             self.seg.gb.zero_()
-        if getattr(self, "_iter_start", None) is None and self.dev.type == "cuda":
-            self._iter_start = torch.cuda.Event()
-        if getattr(self, "_iter_start", None) is not None:
-            self._iter_start.record()     # the previous iteration's optimizer step is queued before it: the packs wait for this, not for the PFN
-            self._prepack_armed = True
+        self._iter_start.record()     # the previous iteration's optimizer step is queued before it: the packs wait for this, not for the PFN
         try:
-            self._forward(points, sample_offsets, batch, grid_ind)
-            losses = []
-            for preds, ncls, tg in self._task_list(targets):
-                order, boxes = self._loss_sources(preds)
-                losses.append(ops.center_loss(preds["hm"], ncls, boxes, tg, self.code_weights, self.loss_weight, with_vel="vel" in preds))
+            self._forward(points, sample_offsets, batch, grid_ind, prev_sweep)
+            losses = self.head_train.losses(targets)
             seg_dlogits = None
             if self._seg_labels is not None:
                 head = self.seg.head
@@ -884,61 +511,34 @@ class PolarPillarTrainStep:
             self._seg_labels = self._point_labels = None
         return loss
 
-    def optimizer_step(self):
-        s = self.sched
-        lr, beta1 = one_cycle(self.iter, s["total"], s["lr_max"], s["moms"], s["div"], s["pct"])
-        total_norm = ops.grad_norm(self.ps.flat_g)
-        ops.adam_step(self.ps.flat_p, self.ps.flat_g, self.ps.flat_m, self.ps.flat_v, self.iter + 1, lr, beta1, self.beta2, self.eps,
-                      self.wd, total_norm=total_norm, max_norm=self.max_norm)
-        self.iter += 1
-        self.invalidate_inference_plans()
-        return total_norm
-
-    # ---- checkpoint / resume (the reference saves model + optimizer state per epoch, det3d/torchie/trainer/trainer.py:342-372)
-    def state_dict(self) -> Dict[str, object]:
-        """optimizer-side state; the parameters themselves are in ``model.state_dict()`` (views of the flat buffer)"""
-        return optimizer_state(self.ps, self.iter, self.sched)
-
-    def load_state_dict(self, state: Dict[str, object]) -> None:
-        self.iter = load_optimizer_state(self.ps, state)
-        self.sched.update(state.get("schedule", {}))
-        self.invalidate_inference_plans()
-
     def invalidate_inference_plans(self):
         invalidate_inference_plans(self.model)
 
     def step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0,
-             point_labels=None):
+             point_labels=None, prev_sweep=None):
         import torch.distributed as dist
-        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        if multi and self.ps.side.on and dist.get_backend() == "gloo":
+        from .dist_utils import BufferSync, GradExchange
+        live = dist.is_available() and dist.is_initialized()
+        world = dist.get_world_size() if live else 1
+        if world > 1 and self.ps.side.on and dist.get_backend() == "gloo":
             # gloo is the transport of the same-GPU dry runs (several ranks on ONE device, tests / bench.py --backend gloo): with the ranks'
             # extra streams the device's hardware queues are oversubscribed across processes and every collective waits for a time slice
             # (1585 against 42 ms per iteration, two ranks on one GPU) -- one stream per rank there
             self.ps.side.on = False
-        return self._step(points, sample_offsets, batch, targets, grid_ind, voxel_labels, seg_loss_scale, point_labels)
-
-    def _step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0,
-              point_labels=None):
-        import torch.distributed as dist
-        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        from .dist_utils import GradExchange
-        # exchange_enabled = False: a timing-only mode of bench.py (the same iteration without the collectives; ranks then diverge)
-        # exchange_at_world_1 = True: the collectives run over a ONE-rank group too (dist_utils.init(single_rank_group=True)): the RCCL path
-        # of a one-GPU box; the result is the no-exchange step's, bit for bit
-        force = bool(getattr(self, "exchange_at_world_1", False)) and world == 1 and dist.is_available() and dist.is_initialized()
-        self._exchange = GradExchange(self.ps.flat_g, self.buckets, force=force) if (world > 1 or force) and getattr(self, "exchange_enabled", True) else None
+        force = self.exchange_at_world_1 and world == 1 and live     # the RCCL path of a one-GPU box; the result is the no-exchange step's, bit for bit
+        exchange = (world > 1 or force) and self.exchange_enabled
+        self._exchange = GradExchange(self.ps.flat_g, self.buckets, force=force) if exchange else None
         # DDP's broadcast_buffers=True (the reference's setting, dist_utils.BufferSync): rank 0's BatchNorm running statistics to every rank
         # at the start of the forward -- one broadcast of one flat tensor, queued in front of the iteration
-        if (world > 1 or force) and getattr(self, "broadcast_buffers", True) and getattr(self, "exchange_enabled", True):
-            if getattr(self, "_bufsync", None) is None:
-                from .dist_utils import BufferSync
+        if exchange and self.broadcast_buffers:
+            if self._bufsync is None:
                 self._bufsync = BufferSync(self.model, self.dev)
             self._bufsync.sync(force=force)
         # the reference averages the gradients over ranks (dist_utils.py:17-28): fold 1/world into the loss gradient
-        try:
-            loss = self._forward_backward(points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world, voxel_labels=voxel_labels,
-                                          seg_loss_scale=seg_loss_scale, point_labels=point_labels)
+        try:    # (this class's forward_backward by name: the streaming step's takes the two sweeps)
+            loss = PolarPillarTrainStep.forward_backward(self, points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world,
+                                                         voxel_labels=voxel_labels, seg_loss_scale=seg_loss_scale, point_labels=point_labels,
+                                                         prev_sweep=prev_sweep)
             if self._exchange is not None:
                 self._exchange.finish()   # the last bucket (reader + first blocks), then the stream waits for all of them
         finally:
@@ -948,9 +548,4 @@ class PolarPillarTrainStep:
 
     def sync_initial_params(self):
         """rank 0's parameters (and BatchNorm running statistics) to every rank, once before the first step"""
-        from .dist_utils import broadcast_flat_params
-        force = bool(getattr(self, "exchange_at_world_1", False))
-        broadcast_flat_params(self.ps.flat_p, force=force)
-        for b in self.model.buffers():
-            if b.dtype.is_floating_point:
-                broadcast_flat_params(b, force=force)
+        self.opt.sync_initial_params(force=bool(self.exchange_at_world_1))

@@ -24,7 +24,7 @@ from . import hip, ops
 from .attention_train import set_block_train
 from .sparse_train import sp_middle_resnet_fhd_train
 from .swv_head_train import e2e_swv_head_train
-from .train import ParamStore, invalidate_inference_plans, one_cycle
+from .train import FlatAdam, OptimizerForwards, ParamStore
 
 
 def rpn_train(t: ad.Tape, neck: nn.Module, x: ad.Node, prefix="neck.") -> ad.Node:
@@ -53,7 +53,7 @@ def rpn_train(t: ad.Tape, neck: nn.Module, x: ad.Node, prefix="neck.") -> ad.Nod
     return ups[0] if len(ups) == 1 else ad.concat_channels(t, ups, sum(u.v.shape[3] for u in ups))
 
 
-class PartnerTrainStep:
+class PartnerTrainStep(OptimizerForwards):
     """``step(example)``: forward (training mode), set criterion, backward, gradient all-reduce (when torch.distributed is
     initialised with world_size > 1), clip + decoupled weight decay + Adam under the OneCycle schedule.  ``example`` carries the
     hard-voxel keys of the reference's collate (voxels (V,P,F), coordinates (V,4) [b,z,y,x], num_points (V,), num_voxels (B,),
@@ -69,14 +69,12 @@ class PartnerTrainStep:
         hip.require_device(p0)
         self.dev = p0.device
         self.ps = ParamStore(model, self.dev)
-        self.sched = dict(total=total_steps, lr_max=lr_max, moms=tuple(moms), div=div_factor, pct=pct_start)
-        self.wd, self.max_norm, self.beta2, self.eps = weight_decay, max_norm, beta2, eps
+        self.opt = FlatAdam(self.ps, model, total_steps, lr_max, moms, div_factor, pct_start, weight_decay, max_norm, beta2, eps)
         # VoxelNetV3 builds its SetBlocks with drop = attn_drop = drop_path = 0.1 (voxelnet.py:192-199)
         self.drop = 0.1 if drop is None else float(drop)
         self.attn_drop = 0.1 if attn_drop is None else float(attn_drop)
         self.drop_path = 0.1 if drop_path is None else float(drop_path)
         self.seed = int(seed)
-        self.iter = 0
         self.last_tape: Optional[ad.Tape] = None
 
     # ------------------------------------------------------------------------------------------
@@ -131,24 +129,8 @@ class PartnerTrainStep:
         hip.call("pn_scale_channels_f32", g.data_ptr(), sc.data_ptr(), g.numel(), g.shape[-1], y.data_ptr(), hip.stream())
         return y
 
-    def optimizer_step(self):
-        s = self.sched
-        lr, beta1 = one_cycle(self.iter, s["total"], s["lr_max"], s["moms"], s["div"], s["pct"])
-        total_norm = ops.grad_norm(self.ps.flat_g)
-        ops.adam_step(self.ps.flat_p, self.ps.flat_g, self.ps.flat_m, self.ps.flat_v, self.iter + 1, lr, beta1, self.beta2, self.eps, self.wd,
-                      total_norm=total_norm, max_norm=self.max_norm)
-        self.iter += 1
-        invalidate_inference_plans(self.model)   # the kernels updated the parameters behind the plans' packed copies (f32 and bf16)
-        return total_norm
-
     def sync_initial_params(self):
-        """rank 0's parameters (and floating-point buffers: BatchNorm running statistics) to every rank, once before the first step
-        -- what DistributedDataParallel's constructor does in the reference (det3d/torchie/apis/train.py:330-336)"""
-        from .dist_utils import broadcast_flat_params
-        broadcast_flat_params(self.ps.flat_p)
-        for b in self.model.buffers():
-            if b.dtype.is_floating_point:
-                broadcast_flat_params(b)
+        self.opt.sync_initial_params()
 
     def step(self, example):
         import torch.distributed as dist

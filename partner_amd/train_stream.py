@@ -16,9 +16,10 @@ det3d/models/necks/rpn_context.py:96-215, under autograd.  Here, without autogra
                        into that map's last row before the layer below consumes it (no pending copy, no separate add); with one sector the
                        padding is circular and both border rows accumulate into rows h - 1 and 0 of the same map.  Rows taken from the
                        previous sweep or from zeros get no gradient.
-``PolarStreamBDCPTrainStep``  ``PolarPillarTrainStep`` with that neck: reader, heads, losses, seg super-task, optimizer, schedule,
-                       checkpoint and gradient buckets are the plain step's.  The previous sweep runs reader + neck in feature-only form
-                       with nothing saved; the rows the streaming pass reads are warped by `pn_polar_warp_strips_f32`.
+``PolarStreamBDCPTrainStep``  ``PolarPillarTrainStep`` built with that neck as its neck part (``neck_train``, also ``ctx_neck``): reader, head
+                       part, losses, seg super-task, optimizer, checkpoint and gradient buckets are the plain step's, and so are the bodies
+                       of ``forward_backward`` and ``step`` -- the previous sweep is their ``prev_sweep`` argument.  It runs reader + neck in
+                       feature-only form with nothing saved; the rows the streaming pass reads are warped by `pn_polar_warp_strips_f32`.
 """
 from __future__ import annotations
 
@@ -28,7 +29,9 @@ import torch
 
 from . import hip, ops
 from .necks_context import RPNBDCP
-from .train import PolarPillarTrainStep, _ConvBNReLU
+from .train import PolarPillarTrainStep
+from .train_layers import _ConvBNReLU
+from .utils.synth import synthetic_iteration      # noqa: F401  (its callers import it from here)
 
 RELU = ops.ACT_RELU
 
@@ -85,13 +88,15 @@ class _CtxLayer:
 
 
 class ContextNeckTrain:
-    """RPNBDCP in training form over a ``ParamStore`` (see the module text).  ``forward_prev`` = the previous sweep's feature-only pass,
-    ``forward`` = the current sweep (all sectors), ``backward`` = its gradients."""
+    """RPNBDCP in training form over a ``ParamStore`` (see the module text): a neck part of the step, with the interface of ``train.RpnTrain``.
+    ``forward_prev`` = the previous sweep's feature-only pass, ``forward`` = the current sweep (all sectors), ``backward`` = its gradients."""
 
-    def __init__(self, ps, neck: RPNBDCP):
+    sparse_first = None     # the sector canvases are dense
+
+    def __init__(self, ps, neck: RPNBDCP, wait_packs=lambda k: None):
         if not isinstance(neck, RPNBDCP):
             raise NotImplementedError("ContextNeckTrain: the neck must be an RPNBDCP")
-        self.ps, self.neck = ps, neck
+        self.ps, self.neck, self.wait_packs = ps, neck, wait_packs
         mods = [cc for blk in neck.blocks for cc in blk._modules.values()]
         self.layers = [_CtxLayer(ps, names, cc) for names, cc in zip(context_layer_names(neck), mods)]
         self.block_of = [names["block"] for names in context_layer_names(neck)]
@@ -100,6 +105,10 @@ class ContextNeckTrain:
         self.up_filters = list(neck._num_upsample_filters)
         self.token = self._prev_token = None
         self.saved = self.de_saved = None
+
+    def early_convs(self):
+        """the deblock fed by block 0: the deblocks' layouts are refreshed on the side stream, the context layers pack on first use"""
+        return [self.deblocks[0].conv] if self.up_start == 0 and self.deblocks else []
 
     # ---------------------------------------------------------------------------------------------------------------- forward
     def forward_prev(self, canvas, nsectors: int):
@@ -115,13 +124,20 @@ class ContextNeckTrain:
             if k + 1 == len(self.layers) or self.block_of[k + 1] != self.block_of[k]:
                 j = self.block_of[k] - self.up_start
                 if j >= 0:
-                    de = self.deblocks[j]
-                    de.fwd(x)
-                    de.conv.x = de.y = de.stat = None
+                    self.deblocks[j].fwd(x)
+                    self.deblocks[j].take_saved()
         return cur
 
-    def forward(self, canvas, nsectors: int, prev_sweep=()):
-        """canvas (nsectors * bs, hs, w, c) stacked sector-major -> the stacked concatenated deblock outputs"""
+    def forward(self, canvas, nsectors: int, prev_sweep=(), prev_canvas=None, warp=None):
+        """canvas (nsectors * bs, hs, w, c) stacked sector-major -> the stacked concatenated deblock outputs.  The previous sweep: its
+        warped rows per layer (``prev_sweep``), or its stacked canvas (``prev_canvas``) and ``warp(layer inputs) -> prev_sweep``: then its
+        feature-only pass runs here first."""
+        self.wait_packs(0)
+        self.wait_packs(1)
+        if prev_canvas is not None:
+            inputs = self.forward_prev(prev_canvas, nsectors)
+            if nsectors > 1:          # one sector pads circularly: the previous sweep's pass only moves the running statistics, as in the reference
+                prev_sweep = warp(inputs)
         self.token, self._prev_token = (self._prev_token or object()), None      # one token per iteration: the packed weights are refreshed once
         n = canvas.shape[0]
         assert n % nsectors == 0
@@ -153,7 +169,7 @@ class ContextNeckTrain:
                             oh, ow = de.conv.layer.out_hw(x.shape[1], x.shape[2])
                             out = torch.empty((n, oh, ow, sum(self.up_filters)), dtype=torch.float32, device=x.device)
                         de.fwd(x, out=out[s * bs:(s + 1) * bs], out_co=sum(self.up_filters[:j]))
-                        self.de_saved[s][j] = (de.conv.x, de.conv.in_co, de.y, de.stat)
+                        self.de_saved[s][j] = de.take_saved()
             ctx = cur
         return out
 
@@ -176,7 +192,7 @@ class ContextNeckTrain:
                     j = self.block_of[k] - self.up_start
                     if j >= 0:
                         de = self.deblocks[j]
-                        de.conv.x, de.conv.in_co, de.y, de.stat = self.de_saved[s][j]
+                        de.restore(self.de_saved[s][j])
                         off = sum(self.up_filters[:j])
                         if d is None:
                             d = de.bwd(d_out[s * bs:(s + 1) * bs], dout_co=off, wacc=wacc)
@@ -215,54 +231,12 @@ class PolarStreamBDCPTrainStep(PolarPillarTrainStep):
         if not isinstance(model, PolarStreamBDCP) or not isinstance(model.neck, RPNBDCP):
             raise NotImplementedError("PolarStreamBDCPTrainStep: the model must be a PolarStreamBDCP with an RPNBDCP neck")
         self.nsec = int(model.nsectors)
-        super().__init__(model, total_steps, **kw)
+        super().__init__(model, total_steps, neck_part=ContextNeckTrain, **kw)
+        self.ctx_neck = self.neck_train
         g = self.spec.grid
         if g[1] % self.nsec:
             raise ValueError(f"the azimuth axis ({g[1]} cells) does not divide into {self.nsec} sectors")
         self.spec = ops.GridSpec(self.spec.lo, self.spec.vs, (g[0], g[1] // self.nsec, g[2]))      # one sector's canvas (detectors._canvas)
-        self._prev = None
-
-    def _build_rpn(self, neck):
-        self.ctx_neck = ContextNeckTrain(self.ps, neck)
-        self.blocks = [[] for _ in neck.blocks]       # the plain step's tables (its pack groups read them): the context layers pack on first use
-        self.deblocks = self.ctx_neck.deblocks
-        self.up_start = neck._upsample_start_idx
-        self.up_filters = list(neck._num_upsample_filters)
-
-    def _sparse_first(self):
-        return None
-
-    def _prev_canvas(self, prev, batch):
-        """reader + scatter of the previous sweep: nothing kept (polarstream.py:318-336, under no_grad)"""
-        spec, r, ps = self.spec, self.reader, self.ps
-        keys = ops.keys_from_grid_ind(prev["grid_ind"].to(torch.int64).contiguous(), spec, batch)
-        vi = ops.build_voxel_index(keys, spec, batch, n_dev=None, want_unq=False, sorted_runs=True)
-        canvas = torch.empty((batch, spec.grid[1], spec.grid[0], r.out_channels), dtype=torch.float32, device=self.dev)
-        hip.call("pn_fill_zero", canvas.data_ptr(), canvas.numel() * 4, hip.stream())
-        ops.dynamic_pfn(prev["points"], vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, None, canvas)
-        return canvas
-
-    def _rpn_forward(self, canvas, batch):
-        nsec = self.nsec
-        assert batch % nsec == 0, "batch is the stacked count nsectors * bs"
-        self._packs_ready(0)
-        self._packs_ready(1)      # the deblocks' layouts are refreshed on the side stream; the context layers pack on first use
-        strips = []
-        if self._prev is not None:
-            inputs = self.ctx_neck.forward_prev(self._prev_canvas(self._prev, batch), nsec)
-            if nsec > 1:          # one sector pads circularly: the previous sweep's pass only moves the running statistics, as in the reference
-                strips = self.model.warp_prev_strips(inputs, self._prev["transform_matrix"], batch // nsec)
-        return self.ctx_neck.forward(canvas, nsec, strips)
-
-    def _rpn_backward(self, d_x2):
-        nblk = len(self.neck.blocks)
-
-        def block_done(i):
-            # a bucket is ready only once its gradients are complete: the neck's blocks are after sector 0's backward
-            if i == nblk - 1 and len(self.buckets) > 2:
-                self._bucket_ready(1)
-
-        return self.ctx_neck.backward(d_x2, block_done=block_done)
 
     def _check_sweeps(self, prev, cur):
         hip.require_device(cur["points"], cur["grid_ind"])
@@ -274,71 +248,9 @@ class PolarStreamBDCPTrainStep(PolarPillarTrainStep):
     def forward_backward(self, prev, cur, batch, targets, grad_scale=1.0, voxel_labels=None, seg_loss_scale=1.0, point_labels=None):
         """-> the det loss vector; gradients in ``ps.flat_g``; ``self.seg_loss`` as in the plain step"""
         self._check_sweeps(prev, cur)
-        self._prev = prev
-        try:
-            return self._forward_backward(cur["points"], None, batch, targets, grid_ind=cur["grid_ind"], grad_scale=grad_scale,
-                                          voxel_labels=voxel_labels, seg_loss_scale=seg_loss_scale, point_labels=point_labels)
-        finally:
-            self._prev = None
+        return super().forward_backward(cur["points"], None, batch, targets, cur["grid_ind"], grad_scale, voxel_labels, seg_loss_scale, point_labels,
+                                        prev_sweep=prev)
 
     def step(self, prev, cur, batch, targets, voxel_labels=None, seg_loss_scale=1.0, point_labels=None):
         self._check_sweeps(prev, cur)
-        self._prev = prev
-        try:
-            return super().step(cur["points"], None, batch, targets, grid_ind=cur["grid_ind"], voxel_labels=voxel_labels,
-                                seg_loss_scale=seg_loss_scale, point_labels=point_labels)
-        finally:
-            self._prev = None
-
-
-def synthetic_iteration(model, bs: int, points_per_sweep: int = 30000, seed: int = 0, angle: float = 0.03, max_objs: int = 500, n_pos: int = 20):
-    """A synthetic two-sweep iteration shaped for ``PolarStreamBDCPTrainStep(model)`` (profiling tool, tests): ``bs`` polar sweeps per sweep
-    slot split into the model's sectors on the device (``ops.split_polar_sectors``), an ego rotation, random CenterPoint targets on the
-    head's map and, with a seg head, labels on ~70 % of the cells that hold points.
-    -> (prev, cur, batch, targets, voxel_labels or None)"""
-    import numpy as np
-    from .utils import synth
-    dev = next(model.parameters()).device
-    nsec, reader = int(model.nsectors), model.reader
-    rng_, vs = [float(v) for v in reader.pc_range], [float(v) for v in reader.voxel_size]
-    batch = nsec * bs
-
-    def sweep(base):
-        sweeps = [synth.synth_sweep_polar(points_per_sweep + 100 * b, seed=base + b, rho_max=min(55.0, rng_[3] - 0.5)) for b in range(bs)]
-        offs = torch.tensor(np.concatenate([[0], np.cumsum([len(s) for s in sweeps])]), dtype=torch.int32, device=dev)
-        out, part, gi, _ = ops.split_polar_sectors(torch.from_numpy(np.concatenate(sweeps, 0)).to(dev), offs, bs, nsec, rng_, vs)
-        po = part.cpu().numpy()
-        n = int(po[batch])
-        gi = gi[:n].clone()
-        for k in range(batch):
-            gi[int(po[k]):int(po[k + 1]), 0] = k                      # stacked sample index, sector-major
-        return dict(points=out[:n].contiguous(), grid_ind=gi.contiguous())
-
-    prev, cur = sweep(1000 + seed), sweep(2000 + seed)
-    c, s = float(np.cos(angle)), float(np.sin(angle))
-    prev["transform_matrix"] = torch.tensor([[[c, -s], [s, c]]] * bs, dtype=torch.float32, device=dev)
-    spec = ops.GridSpec.from_range(rng_, vs)
-    hs, w = spec.grid[1] // nsec, spec.grid[0]
-    neck = model.neck
-    factor = int(round(np.prod(neck._layer_strides[:neck._upsample_start_idx + 1]) / neck._upsample_strides[0]))      # canvas cells per head-map cell
-    h2, w2 = hs // factor, w // factor
-    r = np.random.default_rng(seed)
-    ncls = sum(model.bbox_head.num_classes)
-    hm = (r.uniform(0, 1, (batch, ncls, h2, w2)) ** 8).astype(np.float32)
-    ind, mask = np.zeros((batch, max_objs), np.int64), np.zeros((batch, max_objs), np.uint8)
-    cat, anno = np.zeros((batch, max_objs), np.int64), np.zeros((batch, max_objs, 10), np.float32)
-    for b in range(batch):
-        ind[b, :n_pos] = r.choice(h2 * w2, n_pos, replace=False)
-        mask[b, :n_pos] = 1
-        cat[b, :n_pos] = r.integers(0, ncls, n_pos)
-        anno[b, :n_pos] = r.standard_normal((n_pos, 10)).astype(np.float32)
-        hm[b, cat[b, :n_pos], ind[b, :n_pos] // w2, ind[b, :n_pos] % w2] = 1.0
-    targets = ops.CenterLossTargets(torch.from_numpy(hm), torch.from_numpy(ind), torch.from_numpy(mask), torch.from_numpy(cat), torch.from_numpy(anno), dev)
-    labels = None
-    if getattr(model, "seg_head", None) is not None:
-        cells = torch.unique(cur["grid_ind"][:, [0, 2, 3]], dim=0).cpu().numpy()
-        pick = cells[r.uniform(0, 1, len(cells)) < 0.7]
-        lab = np.zeros((batch, 1, hs, w), np.int64)
-        lab[pick[:, 0], 0, pick[:, 1], pick[:, 2]] = r.integers(1, model.seg_head.num_classes + 1, len(pick))
-        labels = torch.from_numpy(lab).to(dev)
-    return prev, cur, batch, targets, labels
+        return super().step(cur["points"], None, batch, targets, cur["grid_ind"], voxel_labels, seg_loss_scale, point_labels, prev_sweep=prev)

@@ -221,3 +221,56 @@ def load_filled(module, base_seed: int = 0) -> None:
     sd = module.state_dict()
     filled = fill_state_dict(sd, base_seed)
     module.load_state_dict({k: torch.from_numpy(v) for k, v in filled.items()}, strict=True)
+
+
+def synthetic_iteration(model, bs: int, points_per_sweep: int = 30000, seed: int = 0, angle: float = 0.03, max_objs: int = 500, n_pos: int = 20):
+    """A synthetic two-sweep iteration shaped for ``PolarStreamBDCPTrainStep(model)`` (profiling tool, tests): ``bs`` polar sweeps per sweep
+    slot split into the model's sectors on the device (``ops.split_polar_sectors``), an ego rotation, random CenterPoint targets on the
+    head's map and, with a seg head, labels on ~70 % of the cells that hold points.
+    -> (prev, cur, batch, targets, voxel_labels or None)"""
+    import torch
+    from .. import ops
+    dev = next(model.parameters()).device
+    nsec, reader = int(model.nsectors), model.reader
+    rng_, vs = [float(v) for v in reader.pc_range], [float(v) for v in reader.voxel_size]
+    batch = nsec * bs
+
+    def sweep(base):
+        sweeps = [synth_sweep_polar(points_per_sweep + 100 * b, seed=base + b, rho_max=min(55.0, rng_[3] - 0.5)) for b in range(bs)]
+        offs = torch.tensor(np.concatenate([[0], np.cumsum([len(s) for s in sweeps])]), dtype=torch.int32, device=dev)
+        out, part, gi, _ = ops.split_polar_sectors(torch.from_numpy(np.concatenate(sweeps, 0)).to(dev), offs, bs, nsec, rng_, vs)
+        po = part.cpu().numpy()
+        n = int(po[batch])
+        gi = gi[:n].clone()
+        for k in range(batch):
+            gi[int(po[k]):int(po[k + 1]), 0] = k                      # stacked sample index, sector-major
+        return dict(points=out[:n].contiguous(), grid_ind=gi.contiguous())
+
+    prev, cur = sweep(1000 + seed), sweep(2000 + seed)
+    c, s = float(np.cos(angle)), float(np.sin(angle))
+    prev["transform_matrix"] = torch.tensor([[[c, -s], [s, c]]] * bs, dtype=torch.float32, device=dev)
+    spec = ops.GridSpec.from_range(rng_, vs)
+    hs, w = spec.grid[1] // nsec, spec.grid[0]
+    neck = model.neck
+    factor = int(round(np.prod(neck._layer_strides[:neck._upsample_start_idx + 1]) / neck._upsample_strides[0]))      # canvas cells per head-map cell
+    h2, w2 = hs // factor, w // factor
+    r = np.random.default_rng(seed)
+    ncls = sum(model.bbox_head.num_classes)
+    hm = (r.uniform(0, 1, (batch, ncls, h2, w2)) ** 8).astype(np.float32)
+    ind, mask = np.zeros((batch, max_objs), np.int64), np.zeros((batch, max_objs), np.uint8)
+    cat, anno = np.zeros((batch, max_objs), np.int64), np.zeros((batch, max_objs, 10), np.float32)
+    for b in range(batch):
+        ind[b, :n_pos] = r.choice(h2 * w2, n_pos, replace=False)
+        mask[b, :n_pos] = 1
+        cat[b, :n_pos] = r.integers(0, ncls, n_pos)
+        anno[b, :n_pos] = r.standard_normal((n_pos, 10)).astype(np.float32)
+        hm[b, cat[b, :n_pos], ind[b, :n_pos] // w2, ind[b, :n_pos] % w2] = 1.0
+    targets = ops.CenterLossTargets(torch.from_numpy(hm), torch.from_numpy(ind), torch.from_numpy(mask), torch.from_numpy(cat), torch.from_numpy(anno), dev)
+    labels = None
+    if getattr(model, "seg_head", None) is not None:
+        cells = torch.unique(cur["grid_ind"][:, [0, 2, 3]], dim=0).cpu().numpy()
+        pick = cells[r.uniform(0, 1, len(cells)) < 0.7]
+        lab = np.zeros((batch, 1, hs, w), np.int64)
+        lab[pick[:, 0], 0, pick[:, 1], pick[:, 2]] = r.integers(1, model.seg_head.num_classes + 1, len(pick))
+        labels = torch.from_numpy(lab).to(dev)
+    return prev, cur, batch, targets, labels
