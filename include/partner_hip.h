@@ -442,6 +442,33 @@ int pn_conv_border_dgrad_f32(const float *w_oihw, int cout, int cin, int kh, int
                              long long top_sample_stride, int top_pixel_stride, int top_channel_offset, int top_accumulate,
                              float *d_bottom, long long bottom_sample_stride, int bottom_pixel_stride, int bottom_channel_offset,
                              int bottom_accumulate, pn_stream_t stream);
+/* The FORWARD term of the context rows (ConvContext.forward, rpn_context.py:29-43; ConvBDCP.forward 112-162): conv3x3(P) with
+ * P = [top; x; bottom] is the plain pad-1 convolution of x -- same output size, output row oy reads input rows oy*stride - 1 ..
+ * oy*stride + 1 either way -- plus, in output row 0, the ky = 0 taps applied to `top` and, in output row oh - 1, the ky = 2 taps applied
+ * to `bottom`.  `out` NHWC (batch, oh, ow, out_pixel_stride), channels at out_channel_offset, already holds the pad-1 result:
+ *   out[b, 0,      ox, co] += sum_{kw, ci} w[co, ci, 0, kw] * top[b,    ox*stride + kw - 1, ci]
+ *   out[b, oh - 1, ox, co] += sum_{kw, ci} w[co, ci, 2, kw] * bottom[b, ox*stride + kw - 1, ci]     (columns outside [0, in_w) dropped)
+ * A border row is read at ptr[b * sample_stride + x * pixel_stride + channel_offset + ci] (strides in floats): any row of any NHWC map,
+ * e.g. the last row of a saved layer input, without a copy.  Either pointer may be null, not both.  When (in_h - 1) % stride != 0 the
+ * forward never reads the bottom row and nothing is launched for it.  One GEMM per border (M = batch * ow, N = cout, K = 3 * cin) on the
+ * fp32 matrix instructions, the OIHW weight read as it is; fixed summation order (ci chunks, kw), one lane per result, no atomics; with
+ * oh == 1 the two borders are added one launch after the other.  PN_ERR_INVALID without a launch: as pn_conv_border_dgrad_f32. */
+int pn_conv_border_fwd_f32(const float *w_oihw, int cout, int cin, int kh, int kw, int stride, int batch, int in_h, int in_w,
+                           const float *top, long long top_sample_stride, int top_pixel_stride, int top_channel_offset,
+                           const float *bottom, long long bottom_sample_stride, int bottom_pixel_stride, int bottom_channel_offset,
+                           float *out, int oh, int ow, int out_pixel_stride, int out_channel_offset, pn_stream_t stream);
+/* The weight gradient of that term (autograd through the same lines), ADDED into the OIHW gradient tensor dw (cout, cin, 3, 3):
+ *   dw[co, ci, 0, kw] += sum_{b, ox} dout[b, 0,      ox, co] * top[b,    ox*stride + kw - 1, ci]
+ *   dw[co, ci, 2, kw] += sum_{b, ox} dout[b, oh - 1, ox, co] * bottom[b, ox*stride + kw - 1, ci]    (same reachability rule)
+ * the other six (one border: three) taps are not touched.  M = cout, N = cin per width tap, K = batch * ow; the reduction runs in a fixed
+ * order: K is cut into slices, each summed in pixel order; with more than one slice the partial sums go through `workspace`
+ * (pn_conv_border_wgrad_workspace_bytes; 0 = a single slice, workspace may be null) and are added slice by slice, ascending.  No atomics. */
+size_t pn_conv_border_wgrad_workspace_bytes(int cout, int cin, int batch, int ow);
+int pn_conv_border_wgrad_f32(const float *dout, int batch, int oh, int ow, int dout_pixel_stride, int dout_channel_offset, int cout,
+                             int cin, int kh, int kw, int stride, int in_h, int in_w, const float *top, long long top_sample_stride,
+                             int top_pixel_stride, int top_channel_offset, const float *bottom, long long bottom_sample_stride,
+                             int bottom_pixel_stride, int bottom_channel_offset, float *dw_oihw, void *workspace,
+                             size_t workspace_bytes, pn_stream_t stream);
 /* Data gradient = pn_conv2d_nhwc_f32 on dout with re-packed weights:
  *   stride 1:  pack with pn_pack_conv_dgrad_weight_f32 (taps mirrored, Cin/Cout swapped;
  *              pn_conv_packed_weight_floats(cin, cout, kh, kw, 1) floats), run a kh x kw

@@ -278,6 +278,10 @@ SIGNATURES = {
     "pn_conv2d_wino24_chain_head_multi_f32": (_I, [_P, _I, _P]),
     "pn_groupnorm_strat_planes_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P, _SZ, _P]),
     "pn_conv_border_dgrad_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.c_longlong, _I, _I, _I, _P, C.c_longlong, _I, _I, _I, _P]),
+    "pn_conv_border_fwd_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.c_longlong, _I, _I, _P, C.c_longlong, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "pn_conv_border_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "pn_conv_border_wgrad_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.c_longlong, _I, _I, _P, C.c_longlong, _I, _I, _P, _P, _SZ,
+                                      _P]),
     "pn_conv2d_wgrad_wino4_workspace_bytes": (_SZ, [_P]),
     "pn_conv2d_wgrad_wino4_f32": (_I, [_P, _P, _P, _P, _I, _P, _SZ, _P]),
     "pn_pillar_conv_packed_weight_floats": (_SZ, [_I, _I]),

@@ -71,6 +71,43 @@ def conv_border_dgrad(weight: torch.Tensor, dout: torch.Tensor, stride: int, in_
              int(dout_channel_offset), int(in_h), int(in_w), *dst(top), *dst(bottom), hip.stream())
 
 
+def _border_row(t, batch: int, in_w: int):
+    """``(map, row, channel_offset)`` -- row ``row`` of the NHWC ``map`` (B, rows, in_w, C), read in place -- as the C entries' row operand"""
+    if t is None:
+        return (None, 0, 0, 0)
+    m, row, co = t
+    assert m.dim() == 4 and m.is_contiguous() and m.shape[0] == batch and m.shape[2] == in_w and 0 <= row < m.shape[1], (m.shape, row)
+    return (m.data_ptr() + 4 * row * m.stride(1), m.stride(0), m.stride(2), int(co))
+
+
+def conv_border_fwd(weight: torch.Tensor, out: torch.Tensor, stride: int, in_h: int, in_w: int, top=None, bottom=None,
+                    out_channel_offset=0) -> torch.Tensor:
+    """the context rows' term of a context-padded 3x3 convolution, ADDED to ``out`` NHWC (B, OH, OW, Ct), which holds the pad-1 convolution
+    of the (in_h, in_w) centre rows (``pn_conv_border_fwd_f32``).  ``top`` / ``bottom``: None or ``(map, row, channel_offset)``."""
+    hip.require_device(weight, out, None if top is None else top[0], None if bottom is None else bottom[0])
+    assert weight.dim() == 4 and weight.is_contiguous() and out.dim() == 4 and out.is_contiguous()
+    cout, cin, kh, kw = weight.shape
+    b, oh, ow, ct = out.shape
+    hip.call("pn_conv_border_fwd_f32", weight.data_ptr(), cout, cin, kh, kw, int(stride), b, int(in_h), int(in_w), *_border_row(top, b, in_w),
+             *_border_row(bottom, b, in_w), out.data_ptr(), oh, ow, ct, int(out_channel_offset), hip.stream())
+    return out
+
+
+def conv_border_wgrad(dout: torch.Tensor, dw: torch.Tensor, stride: int, in_h: int, in_w: int, top=None, bottom=None,
+                      dout_channel_offset=0) -> torch.Tensor:
+    """the context rows' weight gradient ADDED into the border taps of ``dw`` (Cout, Cin, 3, 3) (``pn_conv_border_wgrad_f32``); dout NHWC
+    (B, OH, OW, Ct) of the convolution's output; ``top`` / ``bottom`` as in ``conv_border_fwd``."""
+    hip.require_device(dout, dw, None if top is None else top[0], None if bottom is None else bottom[0])
+    lib = hip.load()
+    assert dw.dim() == 4 and dw.is_contiguous() and dout.dim() == 4 and dout.is_contiguous()
+    cout, cin, kh, kw = dw.shape
+    b, oh, ow, ct = dout.shape
+    nbytes = lib.pn_conv_border_wgrad_workspace_bytes(cout, cin, b, ow)
+    ws = _workspace(nbytes, dout.device) if nbytes else None
+    hip.call("pn_conv_border_wgrad_f32", dout.data_ptr(), b, oh, ow, ct, int(dout_channel_offset), cout, cin, kh, kw, int(stride), int(in_h),
+             int(in_w), *_border_row(top, b, in_w), *_border_row(bottom, b, in_w), dw.data_ptr(), hip.ptr(ws), nbytes, hip.stream())
+    return dw
+
 
 
 def channel_sum(x: torch.Tensor, c: Optional[int] = None, channel_offset=0, out: Optional[torch.Tensor] = None,

@@ -13,7 +13,7 @@ CenterHeadSinglePos  and one fused clip + decoupled-weight-decay + Adam update o
 parameter buffer.  All arithmetic runs in kernels of libpartner_hip; PyTorch allocates tensors and
 (for world_size > 1) all-reduces the flat gradient buffer through torch.distributed (RCCL).
 
-The step is made of parts: ``ParamStore`` (the flat buffers), a neck part (``RpnTrain`` here, ``train_stream.ContextNeckTrain``), the head
+The step is made of parts: ``ParamStore`` (the flat buffers), a neck part (``RpnTrain`` here, ``train_stream.ContextNeckTrain`` / ``TrailingEdgeNeckTrain``), the head
 part (``train_head.CenterHeadTrain``), the seg head (``seg_heads.SegHeadTrain``) and ``FlatAdam`` (schedule, clip, Adam, checkpoint); the
 layer wrappers they are built from are in ``train_layers``.
 
@@ -516,6 +516,13 @@ class PolarPillarTrainStep(OptimizerForwards):
 
     def step(self, points, sample_offsets, batch, targets: ops.CenterLossTargets, grid_ind=None, voxel_labels=None, seg_loss_scale=1.0,
              point_labels=None, prev_sweep=None):
+        # (this class's forward_backward by name: the streaming steps' take their sweeps in another form)
+        return self._step(lambda scale: PolarPillarTrainStep.forward_backward(
+            self, points, sample_offsets, batch, targets, grid_ind, grad_scale=scale, voxel_labels=voxel_labels, seg_loss_scale=seg_loss_scale,
+            point_labels=point_labels, prev_sweep=prev_sweep))
+
+    def _step(self, forward_backward):
+        """one iteration around ``forward_backward(grad_scale) -> loss``: gradient exchange, buffer broadcast, optimizer step"""
         import torch.distributed as dist
         from .dist_utils import BufferSync, GradExchange
         live = dist.is_available() and dist.is_initialized()
@@ -535,10 +542,8 @@ class PolarPillarTrainStep(OptimizerForwards):
                 self._bufsync = BufferSync(self.model, self.dev)
             self._bufsync.sync(force=force)
         # the reference averages the gradients over ranks (dist_utils.py:17-28): fold 1/world into the loss gradient
-        try:    # (this class's forward_backward by name: the streaming step's takes the two sweeps)
-            loss = PolarPillarTrainStep.forward_backward(self, points, sample_offsets, batch, targets, grid_ind, grad_scale=1.0 / world,
-                                                         voxel_labels=voxel_labels, seg_loss_scale=seg_loss_scale, point_labels=point_labels,
-                                                         prev_sweep=prev_sweep)
+        try:
+            loss = forward_backward(1.0 / world)
             if self._exchange is not None:
                 self._exchange.finish()   # the last bucket (reader + first blocks), then the stream waits for all of them
         finally:

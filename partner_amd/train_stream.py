@@ -20,6 +20,10 @@ det3d/models/necks/rpn_context.py:96-215, under autograd.  Here, without autogra
                        part, losses, seg super-task, optimizer, checkpoint and gradient buckets are the plain step's, and so are the bodies
                        of ``forward_backward`` and ``step`` -- the previous sweep is their ``prev_sweep`` argument.  It runs reader + neck in
                        feature-only form with nothing saved; the rows the streaming pass reads are warped by `pn_polar_warp_strips_f32`.
+
+The trailing-edge detector (PolarStream + RPNTECP, polarstream.py:83-107 over rpn_context.py:46-95) trains through
+``TrailingEdgeNeckTrain`` (the plain step's layers plus the border terms of csrc/conv_border.hip: nothing is assembled) and
+``PolarStreamTrainStep`` (a list of sector examples, one neck call per sector, losses averaged over the sectors); see the classes.
 """
 from __future__ import annotations
 
@@ -217,6 +221,173 @@ class ContextNeckTrain:
         return d_canvas
 
 
+class _BorderLayer(_ConvBNReLU):
+    """one ConvContext of the trailing-edge neck in training form: the plain step's conv + BatchNorm + ReLU layer (every form ``_Conv``
+    selects) plus the border terms of the context row.  ``top``: the input of the same layer in the sector before, whose last row is P's
+    top row -- read in place."""
+
+    def __init__(self, ps, names: Dict[str, str], cc):
+        conv, bn = cc.block[0], cc.block[1]
+        if tuple(conv.kernel_size) != (3, 3) or int(cc.padding) != 1 or conv.bias is not None or conv.stride[0] not in (1, 2):
+            raise NotImplementedError("context-padded training layer: 3x3, padding 1, stride 1 or 2, no bias")
+        assert names["weight"].endswith("block.0.weight")
+        super().__init__(ps, names["weight"][:-len("0.weight")], 0, bn, conv)
+        self.wname, self.stride = names["weight"], int(conv.stride[0])
+
+    def fwd(self, x, top=None):
+        ps = self.ps
+        self.y = self.conv.fwd(x)
+        if top is not None:
+            ops.conv_border_fwd(ps.p[self.wname], self.y, self.stride, x.shape[1], x.shape[2], top=(top, top.shape[1] - 1, 0))
+        res, self.stat = ops.batchnorm_train(self.y, ps.p[self.gname], ps.p[self.bname], self.bn.eps, self.bn.momentum, self.bn.running_mean,
+                                             self.bn.running_var, act=RELU)
+        return res
+
+    def bwd(self, dout, top=None, wacc=False, dx=None):
+        """dout: gradient of the layer's output (own tensor; overwritten with the convolution's output gradient) -> (gradient of the layer's
+        input, the convolution's output gradient)"""
+        ps, x = self.ps, self.conv.x
+        ops.batchnorm_bwd(self.y, dout, ps.p[self.gname], ps.p[self.bname], self.stat, act=RELU, dx=dout, dgamma=ps.g[self.gname],
+                          dbeta=ps.g[self.bname], accumulate=wacc)
+        dy = dout
+        d_in = self.conv.bwd(dy, dx=dx, wacc=wacc)
+        if top is not None:      # behind the layer's weight gradient on the stream that runs it: both add into the same tensor
+            ps.side.run(lambda: ops.conv_border_wgrad(dy, ps.g[self.wname], self.stride, x.shape[1], x.shape[2], top=(top, top.shape[1] - 1, 0)),
+                        dy, top)
+        return d_in, dy
+
+
+class TrailingEdgeNeckTrain:
+    """RPNTECP (rpn_context.py:46-95) in training form over a ``ParamStore``: a neck part of the step, with the interface of
+    ``train.RpnTrain``.  A trailing-edge layer is the plain pad-1 layer plus one row: P = [ctx; x; 0] with ctx the last row of the same
+    layer's input in the sector before, so  conv(P) = conv_pad1(x) + T(ctx)  where T touches output row 0 only.  The layers are
+    the plain step's; per sector s > 0 and layer, `pn_conv_border_fwd_f32` adds T between the convolution and the BatchNorm,
+    `pn_conv_border_wgrad_f32` adds its weight gradient behind the layer's, and `pn_conv_border_dgrad_f32` carries the gradient of ctx into
+    the last row of the earlier sector's input gradient before the layer below consumes it -- nothing is assembled or copied.  BatchNorm
+    statistics are taken per neck call (one per sector, in sector order).
+      ``begin(nsectors)`` / ``forward_sector(canvas)``   one neck call per sector, in streaming order
+      ``forward(canvas, nsectors)``                      all sectors of a canvas stacked sector-major
+      ``backward(d_out, d_canvas, block_done)``          sectors in reverse; ``d_out`` stacked or one tensor per sector"""
+
+    sparse_first = None     # the sector canvases are dense
+
+    def __init__(self, ps, neck, wait_packs=lambda k: None):
+        from .necks_context import RPNTECP
+        if type(neck) is not RPNTECP:
+            raise NotImplementedError("TrailingEdgeNeckTrain: the neck must be an RPNTECP")
+        self.ps, self.neck, self.wait_packs = ps, neck, wait_packs
+        names = context_layer_names(neck)
+        mods = [cc for blk in neck.blocks for cc in blk._modules.values()]
+        self.layers = [_BorderLayer(ps, nm, cc) for nm, cc in zip(names, mods)]
+        self.block_of = [nm["block"] for nm in names]
+        self.deblocks = [_ConvBNReLU(ps, f"neck.deblocks.{j}.", 0, de[1], de[0]) for j, de in enumerate(neck.deblocks)]
+        self.up_start = neck._upsample_start_idx
+        self.up_filters = list(neck._num_upsample_filters)
+        self.block_out: List[torch.Tensor] = []      # the blocks' outputs of the last neck call
+        self.saved = self.de_saved = None
+        self.nsec = self.bs = 0
+
+    def early_convs(self):
+        """block 0 and the deblock fed by block 0"""
+        first = [layer.conv for layer, i in zip(self.layers, self.block_of) if i == 0]
+        return first + ([self.deblocks[0].conv] if self.up_start == 0 and self.deblocks else [])
+
+    def _block_end(self, k: int) -> bool:
+        return k + 1 == len(self.layers) or self.block_of[k + 1] != self.block_of[k]
+
+    # ---------------------------------------------------------------------------------------------------------------- forward
+    def begin(self, nsectors: int):
+        self.nsec, self.bs = int(nsectors), 0
+        self.saved, self.de_saved = [], []
+
+    def forward_sector(self, canvas, out=None):
+        """the next sector's canvas (bs, hs, w, c) -> the concatenated deblock outputs of that sector (written to ``out`` when given)"""
+        s = len(self.saved)
+        assert s < self.nsec, "begin(nsectors) first; one call per sector"
+        self.bs = canvas.shape[0]
+        saved, de_saved, x = [], [None] * len(self.deblocks), canvas
+        self.block_out = []
+        for k, layer in enumerate(self.layers):
+            if k == 0 or self.block_of[k] != self.block_of[k - 1]:
+                if self.block_of[k] < 2:
+                    self.wait_packs(self.block_of[k])
+            x = layer.fwd(x, top=self.saved[s - 1][k][0] if s > 0 else None)
+            saved.append(layer.take_saved())
+            if self._block_end(k):
+                self.block_out.append(x)
+                j = self.block_of[k] - self.up_start
+                if j >= 0:
+                    de = self.deblocks[j]
+                    if out is None:
+                        oh, ow = de.conv.layer.out_hw(x.shape[1], x.shape[2])
+                        out = torch.empty((canvas.shape[0], oh, ow, sum(self.up_filters)), dtype=torch.float32, device=canvas.device)
+                    de.fwd(x, out=out, out_co=sum(self.up_filters[:j]))
+                    de_saved[j] = de.take_saved()
+        self.wait_packs(1)
+        self.saved.append(saved)
+        self.de_saved.append(de_saved)
+        return out
+
+    def forward(self, canvas, nsectors: int = 1):
+        n = canvas.shape[0]
+        assert n % nsectors == 0
+        bs = n // nsectors
+        self.begin(nsectors)
+        out = None
+        for s in range(nsectors):
+            if out is None:
+                first = self.forward_sector(canvas[s * bs:(s + 1) * bs])
+                if nsectors == 1:
+                    return first
+                out = torch.empty((n,) + tuple(first.shape[1:]), dtype=torch.float32, device=canvas.device)
+                out[:bs].copy_(first)
+            else:
+                self.forward_sector(canvas[s * bs:(s + 1) * bs], out=out[s * bs:(s + 1) * bs])
+        return out
+
+    # ---------------------------------------------------------------------------------------------------------------- backward
+    def backward(self, d_out, d_canvas: Optional[torch.Tensor] = None, block_done=None):
+        """d_out: gradient of the sectors' outputs (stacked sector-major, or a list of one tensor per sector) -> gradient of the stacked
+        canvas.  Parameter gradients are OVERWRITTEN by the last sector's call (the first to run) and accumulated by the others;
+        ``block_done(i)`` is called inside sector 0's backward."""
+        nsec, bs, nl = self.nsec, self.bs, len(self.layers)
+        assert len(self.saved) == nsec, "one forward_sector call per sector before backward"
+        first = self.saved[0][0][0]
+        if d_canvas is None:
+            d_canvas = torch.empty((nsec * bs,) + tuple(first.shape[1:]), dtype=torch.float32, device=first.device)
+        later = [None] * nl       # per layer: the convolution-output gradient of the sector after this one, whose top row is this sector's last row
+        for s in range(nsec - 1, -1, -1):
+            wacc = s < nsec - 1
+            d_s = d_out[s] if isinstance(d_out, (list, tuple)) else d_out[s * bs:(s + 1) * bs]
+            d = None
+            for k in range(nl - 1, -1, -1):
+                layer = self.layers[k]
+                if self._block_end(k):        # the block's output: its deblock joins the gradient
+                    j = self.block_of[k] - self.up_start
+                    if j >= 0:
+                        de = self.deblocks[j]
+                        de.restore(self.de_saved[s][j])
+                        off = sum(self.up_filters[:j])
+                        if d is None:
+                            d = de.bwd(d_s, dout_co=off, wacc=wacc)
+                        else:
+                            de.bwd(d_s, dout_co=off, dx=d, accumulate=True, wacc=wacc)
+                layer.restore(self.saved[s][k])
+                x = self.saved[s][k][0]
+                top = self.saved[s - 1][k][0] if s > 0 else None
+                d_in, dy = layer.bwd(d, top=top, wacc=wacc, dx=d_canvas[s * bs:(s + 1) * bs] if k == 0 else None)
+                if later[k] is not None:
+                    ops.conv_border_dgrad(self.ps.p[layer.wname], later[k], layer.stride, x.shape[1], x.shape[2], top=(d_in, x.shape[1] - 1, 0, True))
+                later[k] = dy if s > 0 else None
+                d = d_in
+                layer.take_saved()
+                if s == 0 and block_done is not None and (k == 0 or self.block_of[k - 1] != self.block_of[k]):
+                    block_done(self.block_of[k])
+            self.saved[s] = self.de_saved[s] = None      # (what the side stream still reads is kept by ``ps.side`` until its join)
+        self.saved = self.de_saved = None
+        return d_canvas
+
+
 class PolarStreamBDCPTrainStep(PolarPillarTrainStep):
     """One training iteration of PolarStreamBDCP(DynamicPFNet, DynamicPPScatter, RPNBDCP, <a head of PolarPillarTrainStep>[, SingleConvHead]).
 
@@ -254,3 +425,145 @@ class PolarStreamBDCPTrainStep(PolarPillarTrainStep):
     def step(self, prev, cur, batch, targets, voxel_labels=None, seg_loss_scale=1.0, point_labels=None):
         self._check_sweeps(prev, cur)
         return super().step(cur["points"], None, batch, targets, cur["grid_ind"], voxel_labels, seg_loss_scale, point_labels, prev_sweep=prev)
+
+
+class PolarStreamTrainStep(PolarPillarTrainStep):
+    """One training iteration of the trailing-edge PolarStream(DynamicPFNet, DynamicPPScatter, RPNTECP, <a head of PolarPillarTrainStep>
+    [, SingleConvHead]) on a sweep given as a LIST of sector examples (polarstream.py:83-107 with ``return_loss``: the sectors run one after
+    another, every sector's ``next_context`` -- not detached -- pads the next one, and ``merge_list``, single_stage.py:10-22, averages every
+    loss term over the sectors).
+
+    ``forward_backward(sectors, batch, targets, ...)`` / ``step(...)``: ``sectors`` = one dict(points, grid_ind) per sector in streaming
+    order, each stacked over ``batch`` samples with ``grid_ind`` (n, 4) [sample, z, azimuth, range] relative to the sector's canvas
+    (collate.py:100-107); ``targets`` = one ``CenterLossTargets`` per sector; ``voxel_labels`` / ``point_labels`` = lists of per-sector
+    tensors, or None.  Per sector, in order: index, reader + scatter, neck call, seg head, bbox head, losses -- every module's running
+    statistics move in the reference's order -- and right away the backward of the two heads, which do not couple sectors: what stays for
+    the reverse pass is the sector's ``d_x2`` and the seg head's canvas half.  Every sector's loss gradient carries ``grad_scale / nsec``.
+    The parameter gradients of reader, heads and seg head are summed over the sectors in ``ps.flat_g`` (`pn_add_f32` over the heads' flat
+    range, the reader kernel's accumulate flag); the neck's through ``TrailingEdgeNeckTrain``.  Returns the per-sector det loss vectors
+    stacked (nsec, ...); ``self.seg_loss`` is (nsec, 5); the merged values a trainer logs are their means."""
+
+    def __init__(self, model, total_steps: int, **kw):
+        from .detectors import PolarStream, PolarStreamBDCP
+        from .necks_context import RPNTECP
+        if not isinstance(model, PolarStream) or isinstance(model, PolarStreamBDCP) or type(model.neck) is not RPNTECP:
+            raise NotImplementedError("PolarStreamTrainStep: the model must be a PolarStream with an RPNTECP neck")
+        super().__init__(model, total_steps, neck_part=TrailingEdgeNeckTrain, **kw)
+        self.sweep_spec = self.spec
+        ps = self.ps
+        # the heads' parameters are the tail of the flat buffer (seg head, then bbox head): one range to sum over the sectors
+        self._heads_lo = min((ps.offsets[n][0] for n in ps.names if n.split(".")[0] in ("seg_head", "bbox_head")), default=ps.total)
+        self._heads_sum = torch.empty(ps.total - self._heads_lo, dtype=torch.float32, device=self.dev)
+
+    def _check(self, sectors, targets, voxel_labels, point_labels):
+        if not isinstance(sectors, (list, tuple)) or len(sectors) < 1:
+            raise ValueError("sectors: a list of dict(points, grid_ind), one per sector")
+        nsec = len(sectors)
+        if not isinstance(targets, (list, tuple)) or len(targets) != nsec:
+            raise ValueError(f"{nsec} sectors, but targets is not a list of {nsec} CenterLossTargets")
+        for name, labels in (("voxel_labels", voxel_labels), ("point_labels", point_labels)):
+            if labels is not None and (not isinstance(labels, (list, tuple)) or len(labels) != nsec):
+                raise ValueError(f"{nsec} sectors, but {name} is not a list of {nsec} tensors")
+        if voxel_labels is not None and point_labels is not None:
+            raise ValueError("give voxel_labels or point_labels, not both")
+        if (voxel_labels is not None or point_labels is not None) and self.seg is None:
+            raise ValueError("labels given, but the model has no seg head")
+        g = self.sweep_spec.grid
+        if g[1] % nsec:
+            raise ValueError(f"the azimuth axis ({g[1]} cells) does not divide into {nsec} sectors")
+        for sec in sectors:
+            hip.require_device(sec["points"], sec["grid_ind"])
+        for labels in (voxel_labels, point_labels):
+            if labels is not None:
+                hip.require_device(*labels)
+        return nsec
+
+    def forward_backward(self, sectors, batch, targets, grad_scale=1.0, voxel_labels=None, seg_loss_scale=1.0, point_labels=None):
+        """-> the det loss vectors (nsec, ...); gradients in ``ps.flat_g`` (overwritten); ``self.seg_loss`` (nsec, 5) or None"""
+        from .train import seg_loss_scale_value
+        nsec = self._check(sectors, targets, voxel_labels, point_labels)
+        seg_scale = seg_loss_scale_value(seg_loss_scale)
+        ps, neck, head_train, seg = self.ps, self.neck_train, self.head_train, self.seg
+        g = self.sweep_spec.grid
+        self.nsec = nsec
+        self.spec = spec = ops.GridSpec(self.sweep_spec.lo, self.sweep_spec.vs, (g[0], g[1] // nsec, g[2]))      # one sector's canvas
+        with_seg = voxel_labels is not None or point_labels is not None
+        if point_labels is not None and spec.grid[2] != 1:
+            raise ValueError("point_labels: the seg head's map is 2-D, the grid must have one cell along z")
+        self.seg_loss = None
+        if seg is not None and not with_seg:
+            seg.gw.zero_()
+            seg.gb.zero_()
+        scale = grad_scale / nsec      # the merged loss is the mean over the sectors
+        heads = ps.flat_g[self._heads_lo:]
+        self._iter_start.record()
+        try:
+            neck.begin(nsec)
+            kept, det_losses, seg_losses = [], [], []
+            for s, sec in enumerate(sectors):
+                points = sec["points"]
+                vi = self._index(points, None, batch, sec["grid_ind"])
+                labels = None
+                if point_labels is not None:
+                    assert point_labels[s].numel() == points.shape[0], "point_labels must hold one label per row of points"
+                    labels = ops.voxel_labels_from_points(point_labels[s], vi, dense=False, loss_labels=True).view(batch, spec.grid[1], spec.grid[0])
+                elif voxel_labels is not None:
+                    from .seg_heads import get_labels
+                    assert voxel_labels[s].dim() == 4 and voxel_labels[s].shape[1] == 1, "voxel_labels must be (B, 1, H, W) per sector"
+                    labels = get_labels(voxel_labels[s].squeeze(1), (spec.grid[1], spec.grid[0]))
+                canvas = self._canvas(points, vi, batch)
+                if s == 0:
+                    self._prepack()     # issued behind the first scatter stage's launches, runs beside them
+                x2 = neck.forward_sector(canvas)
+                logits = seg.forward(canvas, x2) if with_seg else None
+                head_train.forward(x2)
+                losses = head_train.losses(targets[s])
+                dlogits = None
+                if with_seg:
+                    sh = seg.head
+                    sl, dlogits = sh.loss_func.loss_and_grad(ops.as_nchw(logits)[:, :sh.num_classes], labels, scale=float(sh.weight) * seg_scale * scale,
+                                                             max_valid=max(int(vi.n_cap), 1))
+                    seg_losses.append(sl)
+                det_losses.append(losses[0] if len(losses) == 1 else torch.stack(losses))
+                # the heads do not couple sectors: their backward runs here; d_x2 (and the seg head's canvas half) wait for the reverse pass
+                self._packs_ready(2)
+                d_x2 = head_train.backward(targets[s], losses, scale)
+                if with_seg:
+                    seg.backward_x2(dlogits, d_x2)
+                    seg.backward_x1(dlogits, need_dx=False)
+                if nsec > 1:      # the heads' parameter gradients, summed in sector order: ((g0 + g1) + g2) + ...
+                    ps.side.join()
+                    if s == 0:
+                        self._heads_sum.copy_(heads)
+                    elif s < nsec - 1:
+                        ops.add(self._heads_sum, heads, out=self._heads_sum)
+                    else:
+                        ops.add(self._heads_sum, heads, out=heads)
+                kept.append((points, vi, d_x2, dlogits))
+            self._bucket_ready(0)   # every head gradient is complete: its exchange overlaps the backward of the neck
+
+            def block_done(i):
+                if i == self.last_block and len(self.buckets) > 2:
+                    self._bucket_ready(1)
+
+            d_canvas = neck.backward([k[2] for k in kept], block_done=block_done)
+            r = self.reader
+            for s in range(nsec - 1, -1, -1):
+                points, vi, _, dlogits = kept[s]
+                d_sec = d_canvas[s * batch:(s + 1) * batch]
+                if dlogits is not None:
+                    seg.backward_canvas(dlogits, d_sec)      # (the canvases of all sectors have one shape: the head's saved one stands for it)
+                ops.dynamic_pfn_bwd(points, vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, d_canvas=d_sec, dw0=ps.g[self.w0],
+                                    dw1=ps.g[self.w1], accumulate=s < nsec - 1)
+            ps.side.join()
+            self.vi = kept[-1][1]
+            if with_seg:
+                self.seg_loss = torch.stack(seg_losses)
+            return torch.stack(det_losses)
+        finally:
+            ps.fresh = None
+            self._pack_events = None
+
+    def step(self, sectors, batch, targets, voxel_labels=None, seg_loss_scale=1.0, point_labels=None):
+        return self._step(lambda scale: self.forward_backward(sectors, batch, targets, grad_scale=scale, voxel_labels=voxel_labels,
+                                                              seg_loss_scale=seg_loss_scale, point_labels=point_labels))

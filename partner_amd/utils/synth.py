@@ -274,3 +274,52 @@ def synthetic_iteration(model, bs: int, points_per_sweep: int = 30000, seed: int
         lab[pick[:, 0], 0, pick[:, 1], pick[:, 2]] = r.integers(1, model.seg_head.num_classes + 1, len(pick))
         labels = torch.from_numpy(lab).to(dev)
     return prev, cur, batch, targets, labels
+
+
+def synthetic_sector_iteration(model, nsec: int, bs: int, points_per_sweep: int = 30000, seed: int = 0, max_objs: int = 500, n_pos: int = 20):
+    """A synthetic iteration shaped for ``PolarStreamTrainStep(model)``: ``bs`` polar sweeps split into ``nsec`` sectors on the device
+    (``ops.split_polar_sectors``) and handed over as the loader does (collate.py:100-107): one dict(points, grid_ind) per sector, stacked over
+    the samples, ``grid_ind`` relative to the sector's canvas; per sector random CenterPoint targets and, with a seg head, labels on ~70 % of
+    the cells that hold points.  -> (sectors, bs, [targets per sector], [voxel_labels per sector] or None)"""
+    import torch
+    from .. import ops
+    dev = next(model.parameters()).device
+    reader = model.reader
+    rng_, vs = [float(v) for v in reader.pc_range], [float(v) for v in reader.voxel_size]
+    sweeps = [synth_sweep_polar(points_per_sweep + 100 * b, seed=2000 + seed + b, rho_max=min(55.0, rng_[3] - 0.5)) for b in range(bs)]
+    offs = torch.tensor(np.concatenate([[0], np.cumsum([len(s) for s in sweeps])]), dtype=torch.int32, device=dev)
+    out, part, gi, _ = ops.split_polar_sectors(torch.from_numpy(np.concatenate(sweeps, 0)).to(dev), offs, bs, nsec, rng_, vs)
+    po = part.cpu().numpy()
+    gi = gi.clone()
+    spec = ops.GridSpec.from_range(rng_, vs)
+    hs, w = spec.grid[1] // nsec, spec.grid[0]
+    neck = model.neck
+    factor = int(round(np.prod(neck._layer_strides[:neck._upsample_start_idx + 1]) / neck._upsample_strides[0]))      # canvas cells per head-map cell
+    h2, w2 = hs // factor, w // factor
+    r = np.random.default_rng(seed)
+    ncls = sum(model.bbox_head.num_classes)
+    seg = getattr(model, "seg_head", None)
+    sectors, targets, labels = [], [], []
+    for sec in range(nsec):
+        for b in range(bs):
+            gi[int(po[sec * bs + b]):int(po[sec * bs + b + 1]), 0] = b          # the sample index inside the sector's example
+        lo, hi = int(po[sec * bs]), int(po[(sec + 1) * bs])
+        sectors.append(dict(points=out[lo:hi].contiguous(), grid_ind=gi[lo:hi].contiguous()))
+        hm = (r.uniform(0, 1, (bs, ncls, h2, w2)) ** 8).astype(np.float32)
+        ind, mask = np.zeros((bs, max_objs), np.int64), np.zeros((bs, max_objs), np.uint8)
+        cat, anno = np.zeros((bs, max_objs), np.int64), np.zeros((bs, max_objs, 10), np.float32)
+        for b in range(bs):
+            ind[b, :n_pos] = r.choice(h2 * w2, n_pos, replace=False)
+            mask[b, :n_pos] = 1
+            cat[b, :n_pos] = r.integers(0, ncls, n_pos)
+            anno[b, :n_pos] = r.standard_normal((n_pos, 10)).astype(np.float32)
+            hm[b, cat[b, :n_pos], ind[b, :n_pos] // w2, ind[b, :n_pos] % w2] = 1.0
+        targets.append(ops.CenterLossTargets(torch.from_numpy(hm), torch.from_numpy(ind), torch.from_numpy(mask), torch.from_numpy(cat),
+                                             torch.from_numpy(anno), dev))
+        if seg is not None:
+            cells = torch.unique(sectors[-1]["grid_ind"][:, [0, 2, 3]], dim=0).cpu().numpy()
+            pick = cells[r.uniform(0, 1, len(cells)) < 0.7]
+            lab = np.zeros((bs, 1, hs, w), np.int64)
+            lab[pick[:, 0], 0, pick[:, 1], pick[:, 2]] = r.integers(1, seg.num_classes + 1, len(pick))
+            labels.append(torch.from_numpy(lab).to(dev))
+    return sectors, bs, targets, (labels if seg is not None else None)
