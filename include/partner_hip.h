@@ -36,6 +36,10 @@ extern "C" {
 #define PN_ERR_LAUNCH (-2)    /* HIP reported a launch error                   */
 #define PN_ERR_WORKSPACE (-3) /* workspace too small                           */
 
+/* voxel shapes of DynamicPFNet.feature_deco (the *_shape entries of V4 below) */
+#define PN_VOXEL_CYLINDER 0
+#define PN_VOXEL_CUBOID 1
+
 #define PN_ACT_NONE 0
 #define PN_ACT_RELU 1
 #define PN_ACT_TANH 2
@@ -69,6 +73,12 @@ int pn_handle_pci_bus_id(pn_handle_t handle, char *buf, size_t buf_len);
  * once to fp32 (differs from glibc atan2f by at most 1 ulp).
  */
 int pn_cart_to_polar_f32(const float *cart, int n, int f_in, float *polar, pn_stream_t stream);
+/* The cuboid branch, transform_points(pc,'cuboid')  det3d/datasets/pipelines/utils.py:45-47
+ * cart: (n, f_in>=3) [x,y,z,rest...]  ->  out: (n, f_in+2) [x,y,z,rest...,rho,phi]
+ * rho and phi by the arithmetic of pn_cart_to_polar_f32 (one per-point device function serves both): the two calls write the same
+ * bits for the same point.  The Cartesian grid index needs no entry of its own: pn_polar_grid_index_f32 indexes columns 0:3
+ * against whatever range it is given. */
+int pn_cart_to_cuboid_f32(const float *cart, int n, int f_in, float *out, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * V1  dynamic voxelization indices.
@@ -213,7 +223,7 @@ int pn_concat_voxel_segments_f32(const float *feats, const int32_t *coors, const
                                  int32_t *total, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * V4 (+V5)  DynamicPFNet forward, cylinder grid, full decoration (16 channels):
+ * V4 (+V5)  DynamicPFNet forward, full decoration (16 channels); this entry: the cylinder grid, the *_shape entries below: either shape:
  *   [points(7) | xyz-mean_voxel(3) | x-xc, y-yc | (rho,phi)-mean_voxel(2) | rho-rc, phi-pc]
  *   -> Linear(16->C0, no bias) ReLU segmax, concat -> Linear(2*C0->C1, no bias) ReLU segmax
  * Replaces DynamicPFNet.forward / feature_deco / PFNLayer.forward_dynamic / get_cluster /
@@ -233,6 +243,22 @@ int pn_dynamic_pfn_fwd(const float *points, int point_stride, const int32_t *vox
                        const float *w1, int c1, float vx, float vy, float x_offset, float y_offset,
                        float *features, float *canvas, pn_stream_t stream);
 
+/* The same for either voxel shape of feature_deco (pillar_encoder.py:338-391).  Both decorations have one form,
+ *   d[16] = { p0..p6, a-ma, b-mb, c-mc, a-ca, b-cb, e-me, f-mf, e-ce, f-cf },
+ * (a, b, c) the "xyz" columns of the point row, (e, f) its "ra" columns, m* the pillar means, (ca, cb) / (ce, cf) the pillar centre
+ * in the two coordinate systems; c1 = ix*vx + x_offset, c2 = iy*vy + y_offset:
+ *   PN_VOXEL_CYLINDER  (a,b,c,e,f) = columns 3,4,2,0,1   (ca,cb) = c1 cos c2, c1 sin c2   (ce,cf) = c1, c2
+ *   PN_VOXEL_CUBOID    (a,b,c,e,f) = columns 0,1,2,5,6   (ca,cb) = c1, c2                 (ce,cf) = sqrt(c1^2 + c2^2), atan2(c2, c1)
+ * The cuboid's radius is torch.sqrt(c1 ** 2 + c2 ** 2) in IEEE fp32 (products and sum rounded separately), its angle follows
+ * pn_cart_to_polar_f32's rule (fp64, rounded once).  The decoration goes by column index only: a cuboid reader over polar-layout
+ * rows and a polar grid is what the reference's streaming configs compute, and is computed as such.  Any other voxel_shape:
+ * PN_ERR_INVALID, nothing launched.  pn_dynamic_pfn_fwd is this call with PN_VOXEL_CYLINDER. */
+int pn_dynamic_pfn_fwd_shape(const float *points, int point_stride, const int32_t *voxel_start,
+                             const int32_t *order, const int32_t *num_voxels, int v_capacity,
+                             const uint32_t *unq_keys, const int32_t *grid, const float *w0, int c0,
+                             const float *w1, int c1, float vx, float vy, float x_offset, float y_offset,
+                             int voxel_shape, float *features, float *canvas, pn_stream_t stream);
+
 /* cos/sin table of the pillar-centre azimuths (2*T floats) and the table-driven variant of the call
  * above (register-resident weights for the reference's C0 = 32, C1 = 128 reader) */
 size_t pn_pfn_center_table_floats(int t);
@@ -251,6 +277,22 @@ int pn_dynamic_pfn_fwd_table_clear(const float *points, int point_stride, const 
                                    const float *w1, int c1, float vx, float vy, float x_offset,
                                    float y_offset, const float *center_table, float *features,
                                    float *canvas, uint32_t *cell_count, pn_stream_t stream);
+
+/* The two calls above with the voxel shape of feature_deco (pillar_encoder.py:338-391; see pn_dynamic_pfn_fwd_shape).  The cuboid
+ * does not read center_table, which may be NULL there; the old entries are these with PN_VOXEL_CYLINDER. */
+int pn_dynamic_pfn_fwd_table_shape(const float *points, int point_stride, const int32_t *voxel_start,
+                                   const int32_t *order, const int32_t *num_voxels, int v_capacity,
+                                   const uint32_t *unq_keys, const int32_t *grid, const float *w0, int c0,
+                                   const float *w1, int c1, float vx, float vy, float x_offset,
+                                   float y_offset, const float *center_table, int voxel_shape,
+                                   float *features, float *canvas, pn_stream_t stream);
+int pn_dynamic_pfn_fwd_table_clear_shape(const float *points, int point_stride, const int32_t *voxel_start,
+                                         const int32_t *order, const int32_t *num_voxels, int v_capacity,
+                                         const uint32_t *unq_keys, const int32_t *grid, const float *w0,
+                                         int c0, const float *w1, int c1, float vx, float vy, float x_offset,
+                                         float y_offset, const float *center_table, int voxel_shape,
+                                         float *features, float *canvas, uint32_t *cell_count,
+                                         pn_stream_t stream);
 
 /* pointer to the uint32 key-per-voxel array inside a pn_unique_rank_bitmap workspace */
 const uint32_t *pn_unique_keys_ptr(const void *workspace, uint64_t num_cells, int n_capacity);
@@ -282,6 +324,16 @@ int pn_dynamic_pfn_bwd(const float *points, int point_stride, const int32_t *vox
                        const float *center_table, const float *d_features, const float *d_canvas,
                        float *dw0, float *dw1, int accumulate, void *workspace,
                        size_t workspace_bytes, pn_stream_t stream);
+
+/* The same with the voxel shape of feature_deco (pillar_encoder.py:338-391; see pn_dynamic_pfn_fwd_shape): the backward recomputes the
+ * decoration of that shape.  center_table may be NULL for PN_VOXEL_CUBOID.  pn_dynamic_pfn_bwd is this call with PN_VOXEL_CYLINDER. */
+int pn_dynamic_pfn_bwd_shape(const float *points, int point_stride, const int32_t *voxel_start,
+                             const int32_t *order, const int32_t *num_voxels, int v_capacity,
+                             const uint32_t *unq_keys, const int32_t *grid, const float *w0, int c0,
+                             const float *w1, int c1, float vx, float vy, float x_offset, float y_offset,
+                             const float *center_table, int voxel_shape, const float *d_features,
+                             const float *d_canvas, float *dw0, float *dw1, int accumulate, void *workspace,
+                             size_t workspace_bytes, pn_stream_t stream);
 
 /* V5 alone: DynamicPPScatter.forward (pillar_encoder.py:418-432) / PointPillarsScatter
  * features (V x C), unq int64 (V x 4) -> canvas NHWC (batch,T,R,C); caller zero-fills. */

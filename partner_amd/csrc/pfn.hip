@@ -79,9 +79,54 @@ struct PfnArgs {
   uint32_t* cell_count;      // nullable (r6, the (32, 128) kernels): the frame index's per-cell counters, zeroed for this frame's voxels on the way
 };
 
+// ---- the two voxel shapes of feature_deco (pillar_encoder.py:338-391) ---------------------------
+// Both decorations are  d[16] = { p0..p6, a-ma, b-mb, c-mc, a-ca, b-cb, e-me, f-mf, e-ce, f-cf }  with (a, b, c) the "xyz" columns of the
+// point row, (e, f) its "ra" columns, m* the pillar means and (ca, cb) / (ce, cf) the pillar centre in the two coordinate systems.  With
+// c1 = ix vx + x_offset, c2 = iy vy + y_offset:
+//   cylinder  (a, b, c, e, f) = columns 3, 4, 2, 0, 1   (ca, cb) = c1 cos c2, c1 sin c2   (ce, cf) = c1, c2
+//   cuboid    (a, b, c, e, f) = columns 0, 1, 2, 5, 6   (ca, cb) = c1, c2                 (ce, cf) = sqrt(c1^2 + c2^2), atan2(c2, c1)
+// The kernels below name the roles as the cylinder does (x y z rho phi, mx my mz mr mp, xc yc rc pc); the shape is a compile-time
+// parameter, so the cylinder instantiations are the code they were before the cuboid existed.
+// Fixed-point means: the cuboid's "ra" columns are whatever the row carries in columns 5 and 6 -- intensity (up to 255 in nuScenes) and
+// the time lag with the reference's streaming configs, rho (< 2^7) and phi after pn_cart_to_cuboid_f32.  The int64 sums of to_fix stay in
+// range at the largest pillar the block-per-pillar kernel is given (20000 points in the tests): 255 * 2^24 * 20000 < 2^8 * 2^24 * 2^15
+// = 2^47 < 2^63 -- and still would with a whole 2^22-point frame in one pillar (2^54).
+constexpr int kCylinder = PN_VOXEL_CYLINDER, kCuboid = PN_VOXEL_CUBOID;
+template <int SHAPE>
+struct Cols {
+  static_assert(SHAPE == kCylinder || SHAPE == kCuboid, "voxel shape");
+  static constexpr int X = SHAPE == kCuboid ? 0 : 3, Y = SHAPE == kCuboid ? 1 : 4, Z = 2;
+  static constexpr int R = SHAPE == kCuboid ? 5 : 0, P = SHAPE == kCuboid ? 6 : 1;
+};
+
+// polar coordinates of a cuboid pillar's centre, as torch.sqrt(c1 ** 2 + c2 ** 2), torch.atan2(c2, c1) (pillar_encoder.py:380-381): the
+// products and the sum rounded separately in fp32; the angle by pn_cart_to_polar_f32's rule (fp64, rounded once).  Once per pillar.
+__device__ __forceinline__ void cuboid_centre_polar(float c1, float c2, float& rc, float& pc) {
+  rc = __fsqrt_rn(__fadd_rn(__fmul_rn(c1, c1), __fmul_rn(c2, c2)));
+  pc = (float)atan2((double)c2, (double)c1);
+}
+
+// pillar centre (ri, ti) in polar (rc, pc) and Cartesian (xc, yc) coordinates (pillar_encoder.py:350-351,365 / 347-348,380-381).  The
+// cylinder takes cos / sin of its azimuth from the table of pn_pfn_center_table_f32; the cuboid does not read it (it may be NULL).
+template <int SHAPE>
+__device__ __forceinline__ void pillar_centre(const PfnArgs& a, const float* __restrict__ cs_table, int ri, int ti, float& rc, float& pc,
+                                              float& xc, float& yc) {
+  const float c1 = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
+  const float c2 = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
+  if constexpr (SHAPE == kCuboid) {
+    xc = c1; yc = c2;
+    cuboid_centre_polar(c1, c2, rc, pc);
+  } else {
+    rc = c1; pc = c2;
+    xc = __fmul_rn(rc, cs_table[2 * ti]); yc = __fmul_rn(rc, cs_table[2 * ti + 1]);
+  }
+}
+
 constexpr int kPfnWaves = 8;  // 8 waves share one LDS copy of the weights: 4 blocks (32 waves) per CU
 
+template <int SHAPE>
 __global__ __launch_bounds__(kPfnWaves * 64) void dynamic_pfn_kernel(PfnArgs a) {
+  using D = Cols<SHAPE>;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int c0 = a.c0, c1 = a.c1;
   float* w0t = lds;                 // [16][c0]
@@ -118,21 +163,28 @@ __global__ __launch_bounds__(kPfnWaves * 64) void dynamic_pfn_kernel(PfnArgs a) 
     long long sx = 0, sy = 0, sz = 0, sr = 0, sp = 0;
     for (int i = s + lane; i < e; i += 64) {
       const float* p = a.pts + (size_t)a.order[i] * a.stride;
-      sr += to_fix(p[0]); sp += to_fix(p[1]); sz += to_fix(p[2]); sx += to_fix(p[3]); sy += to_fix(p[4]);
+      sr += to_fix(p[D::R]); sp += to_fix(p[D::P]); sz += to_fix(p[D::Z]); sx += to_fix(p[D::X]); sy += to_fix(p[D::Y]);
     }
     const double inv_n = 1.0 / ((double)(e - s) * kFix);
     const float mx = (float)((double)pn::wave_sum(sx) * inv_n), my = (float)((double)pn::wave_sum(sy) * inv_n);
     const float mz = (float)((double)pn::wave_sum(sz) * inv_n), mr = (float)((double)pn::wave_sum(sr) * inv_n);
     const float mp = (float)((double)pn::wave_sum(sp) * inv_n);
     // pillar centre in polar and Cartesian coordinates (pillar_encoder.py:350-351,365)
-    const float rc = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
-    const float pc = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
-    const float xc = __fmul_rn(rc, cosf(pc)), yc = __fmul_rn(rc, sinf(pc));
+    const float cen1 = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
+    const float cen2 = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
+    float rc, pc, xc, yc;      // (no azimuth table in this kernel: the cylinder takes cos / sin itself)
+    if constexpr (SHAPE == kCuboid) {
+      xc = cen1; yc = cen2;
+      cuboid_centre_polar(cen1, cen2, rc, pc);
+    } else {
+      rc = cen1; pc = cen2;
+      xc = __fmul_rn(rc, cosf(pc)); yc = __fmul_rn(rc, sinf(pc));
+    }
 
     auto layer0 = [&](const float* p) -> float {
       // 16-channel decoration of one point, then row `lane` of Linear(16 -> c0) + ReLU
-      const float rho = p[0], phi = p[1], z = p[2], x = p[3], y = p[4];
-      const float d[16] = {rho, phi, z, x, y, p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc,
+      const float rho = p[D::R], phi = p[D::P], z = p[D::Z], x = p[D::X], y = p[D::Y];
+      const float d[16] = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc,
                            rho - mr, phi - mp, rho - rc, phi - pc};
       float h = 0.f;
       if (lane < c0) {
@@ -199,7 +251,9 @@ constexpr int kFwdPoints = 1024; // point rows staged in LDS per sub-batch (>= k
 // consecutive pillars -- their points are one consecutive range of order[] -- and stages run bounds, keys and the point
 // rows in LDS with all 256 threads loading in parallel (three latencies per BATCH); each wave then works through its
 // share of the pillars from LDS.  A batch whose points exceed the LDS rows is cut into sub-batches at pillar boundaries.
+template <int SHAPE>
 __device__ __forceinline__ void pfn_32_128_main(const PfnArgs& a, const float* __restrict__ cs_table, const int bid, const int nblk) {
+  using D = Cols<SHAPE>;
   constexpr int NB = kFwdBatch, CAP = kFwdPoints;
   static_assert(CAP >= kHeavyPillar, "a non-heavy pillar must fit the staging rows");
   __shared__ int m_s[NB], m_e[NB];
@@ -254,17 +308,13 @@ __device__ __forceinline__ void pfn_32_128_main(const PfnArgs& a, const float* _
         long long sx = 0, sy = 0, sz = 0, sr = 0, sp = 0;
         for (int i = s; i < e; ++i) {
           const float* p = p_l[i];
-          sr += to_fix(p[0]); sp += to_fix(p[1]); sz += to_fix(p[2]); sx += to_fix(p[3]); sy += to_fix(p[4]);
+          sr += to_fix(p[D::R]); sp += to_fix(p[D::P]); sz += to_fix(p[D::Z]); sx += to_fix(p[D::X]); sy += to_fix(p[D::Y]);
         }
         const double inv_n = 1.0 / ((double)(e - s) * kFix);
         float* c = m_c[q];
         c[0] = (float)((double)sx * inv_n); c[1] = (float)((double)sy * inv_n); c[2] = (float)((double)sz * inv_n);
         c[3] = (float)((double)sr * inv_n); c[4] = (float)((double)sp * inv_n);
-        const float rc = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
-        c[5] = rc;
-        c[6] = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
-        c[7] = __fmul_rn(rc, cs_table[2 * ti]);
-        c[8] = __fmul_rn(rc, cs_table[2 * ti + 1]);
+        pillar_centre<SHAPE>(a, cs_table, ri, ti, c[5], c[6], c[7], c[8]);
         c[9] = __builtin_bit_cast(float, (bi * a.T + ti) * a.R + ri);
       }
       __syncthreads();
@@ -275,8 +325,8 @@ __device__ __forceinline__ void pfn_32_128_main(const PfnArgs& a, const float* _
         const float mx = c[0], my = c[1], mz = c[2], mr = c[3], mp = c[4], rc = c[5], pc = c[6], xc = c[7], yc = c[8];
         const int cell = __builtin_bit_cast(int, c[9]);
         auto layer0 = [&](const float* p) -> float {
-          const float rho = p[0], phi = p[1], z = p[2], x = p[3], y = p[4];
-          const float d[16] = {rho, phi, z, x, y, p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc,
+          const float rho = p[D::R], phi = p[D::P], z = p[D::Z], x = p[D::X], y = p[D::Y];
+          const float d[16] = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc,
                                rho - mr, phi - mp, rho - rc, phi - pc};
           float h = 0.f;
 #pragma unroll
@@ -340,8 +390,9 @@ __device__ __forceinline__ void pfn_32_128_main(const PfnArgs& a, const float* _
 // sweep): one 8-wave block per pillar, the three phases (means, layer-0 maxima, layer-1 maxima)
 // meet in LDS.  Sums are exact int64 and maxima order independent, so the values are bit-identical
 // to what the one-wave path would have produced.
-template <int TH = kHeavyPillar>      // pillars with more than TH points (the tile path hands over at 16)
+template <int SHAPE, int TH = kHeavyPillar>      // pillars with more than TH points (the tile path hands over at 16)
 __device__ __forceinline__ void pfn_32_128_heavy(const PfnArgs& a, const float* __restrict__ cs_table, const int bid, const int nblk) {
+  using D = Cols<SHAPE>;
   __shared__ long long part_sum[kHeavyWaves][5];
   __shared__ float part_max[kHeavyWaves][128];
   __shared__ int heavy_list[kHeavyWaves * 64];
@@ -380,7 +431,7 @@ __device__ __forceinline__ void pfn_32_128_heavy(const PfnArgs& a, const float* 
     long long sx = 0, sy = 0, sz = 0, sr = 0, sp = 0;
     for (int i = s + (int)threadIdx.x; i < e; i += kHeavyWaves * 64) {
       const float* p = a.pts + (size_t)a.order[i] * a.stride;
-      sr += to_fix(p[0]); sp += to_fix(p[1]); sz += to_fix(p[2]); sx += to_fix(p[3]); sy += to_fix(p[4]);
+      sr += to_fix(p[D::R]); sp += to_fix(p[D::P]); sz += to_fix(p[D::Z]); sx += to_fix(p[D::X]); sy += to_fix(p[D::Y]);
     }
     sx = pn::wave_sum(sx); sy = pn::wave_sum(sy); sz = pn::wave_sum(sz); sr = pn::wave_sum(sr); sp = pn::wave_sum(sp);
     if (lane == 0) { part_sum[wib][0] = sx; part_sum[wib][1] = sy; part_sum[wib][2] = sz; part_sum[wib][3] = sr; part_sum[wib][4] = sp; }
@@ -393,12 +444,11 @@ __device__ __forceinline__ void pfn_32_128_heavy(const PfnArgs& a, const float* 
     const double inv_n = 1.0 / ((double)(e - s) * kFix);
     const float mx = (float)((double)t[0] * inv_n), my = (float)((double)t[1] * inv_n), mz = (float)((double)t[2] * inv_n);
     const float mr = (float)((double)t[3] * inv_n), mp = (float)((double)t[4] * inv_n);
-    const float rc = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
-    const float pc = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
-    const float xc = __fmul_rn(rc, cs_table[2 * ti]), yc = __fmul_rn(rc, cs_table[2 * ti + 1]);
+    float rc, pc, xc, yc;
+    pillar_centre<SHAPE>(a, cs_table, ri, ti, rc, pc, xc, yc);
     auto layer0 = [&](const float* p) -> float {
-      const float rho = p[0], phi = p[1], z = p[2], x = p[3], y = p[4];
-      const float d[16] = {rho, phi, z, x, y, p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc,
+      const float rho = p[D::R], phi = p[D::P], z = p[D::Z], x = p[D::X], y = p[D::Y];
+      const float d[16] = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc,
                            rho - mr, phi - mp, rho - rc, phi - pc};
       float h = 0.f;
 #pragma unroll
@@ -472,9 +522,11 @@ constexpr int kW1bPitch = 36;                               // 36 rho mod 64 are
 #ifndef PN_PFN_EXP
 #define PN_PFN_EXP 0      // diagnostic builds (-DPN_PFN_EXP=k): 1 no groups at all, 2 layer 1 cut to one K step, 16 rows staged in memory order, 32 no point loads, 64 no fixed-point sums, 128 no pillars (prologue only), 512 no azimuth table -- wrong results, times only
 #endif
+template <int SHAPE>
 __device__ __forceinline__ void pfn_32_128_tiles(const PfnArgs& a, const float* __restrict__ cs_table, const int bid, const int nblk) {
   // the batch is up to 256 pillars (one per thread), sized from the frame: a 64-pillar batch of a dense multi-sweep frame is ~110 point rows behind
   // three barrier-separated latency phases (run bounds -> order -> point rows; the per-pillar scalars)
+  using D = Cols<SHAPE>;
   using f32x4 = __attribute__((ext_vector_type(4))) float;
   using i32x4 = __attribute__((ext_vector_type(4))) int;
   constexpr int NBMAX = kTileBatchMax, CAP = kFwdPoints;
@@ -516,8 +568,11 @@ __device__ __forceinline__ void pfn_32_128_tiles(const PfnArgs& a, const float* 
 #pragma unroll
       for (int i = 0; i < 8; ++i) a1h[mt][i] = w1s[(16 * mt + rho) * 64 + ((4 * i + jj) ^ (4 * rho))];
   }      // (the batch loop opens with a barrier: every wave has its fragments before the rows are staged)
-  const int p1_idx = jj == 3 ? 3 : 4 + jj;                                      // y p5 p6 x
-  const int p2_idx = jj == 0 ? 4 : jj == 1 ? 2 : jj == 2 ? 3 : 4;              // y z x y
+  // (the point components follow the voxel shape; the m_c record is by ROLE -- mx my mz mr mp rc pc xc yc for either shape -- so the pillar
+  // scalars a lane picks do not)
+  const int p1_idx = jj == 3 ? D::X : 4 + jj;                                   // p4 p5 p6 x
+  const int p2_idx = jj == 0 ? D::Y : jj == 1 ? D::Z : jj == 2 ? D::X : D::Y;  // y z x y
+  static_assert(D::P == D::R + 1, "the ra columns are neighbours: lane group jj reads column R + (jj & 1) below (rho phi rho phi)");
   const int c2_idx = jj == 0 ? 1 : jj == 1 ? 2 : jj == 2 ? 7 : 8;              // my mz xc yc
   const float* w1b_l = w1b_s + rho * kW1bPitch + jj;      // + 16 mt pitch + 4 i: row 16 mt + rho, column 32 + 4 i + jj
   for (int v0 = bid * NB; v0 < V; v0 += nblk * NB) {
@@ -574,17 +629,21 @@ __device__ __forceinline__ void pfn_32_128_tiles(const PfnArgs& a, const float* 
         long long sx = 0, sy = 0, sz = 0, sr = 0, sp = 0;
         for (int i = s; i < e; ++i) {
           const float* p = p_l[i];
-          if (!(PN_PFN_EXP & 64)) { sr += to_fix(p[0]); sp += to_fix(p[1]); sz += to_fix(p[2]); sx += to_fix(p[3]); sy += to_fix(p[4]); }
+          if (!(PN_PFN_EXP & 64)) { sr += to_fix(p[D::R]); sp += to_fix(p[D::P]); sz += to_fix(p[D::Z]); sx += to_fix(p[D::X]); sy += to_fix(p[D::Y]); }
         }
         const double inv_n = 1.0 / ((double)(e - s) * kFix);
         float* c = m_c[q];
         c[0] = (float)((double)sx * inv_n); c[1] = (float)((double)sy * inv_n); c[2] = (float)((double)sz * inv_n);
         c[3] = (float)((double)sr * inv_n); c[4] = (float)((double)sp * inv_n);
-        const float rc = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
-        c[5] = rc;
-        c[6] = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
-        c[7] = (PN_PFN_EXP & 512) ? rc : __fmul_rn(rc, cs_table[2 * ti]);
-        c[8] = (PN_PFN_EXP & 512) ? rc : __fmul_rn(rc, cs_table[2 * ti + 1]);
+        if constexpr (SHAPE == kCuboid) {
+          pillar_centre<SHAPE>(a, cs_table, ri, ti, c[5], c[6], c[7], c[8]);
+        } else {      // (pillar_centre<kCylinder> with the diagnostic build's switch in it)
+          const float rc = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
+          c[5] = rc;
+          c[6] = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
+          c[7] = (PN_PFN_EXP & 512) ? rc : __fmul_rn(rc, cs_table[2 * ti]);
+          c[8] = (PN_PFN_EXP & 512) ? rc : __fmul_rn(rc, cs_table[2 * ti + 1]);
+        }
         c[9] = __builtin_bit_cast(float, (bi * a.T + ti) * a.R + ri);
         int place = my_slot;
 #pragma unroll
@@ -614,7 +673,7 @@ __device__ __forceinline__ void pfn_32_128_tiles(const PfnArgs& a, const float* 
         const float c1 = mc[0], c2 = mc[c2_idx], c3 = mc[3 + jj];      // (c1: mx, used by lane group 3 only)
         auto layer0 = [&](int j, f32x4 (&h)[2]) {
           const float* pr = p_l[row0 + min(j, last)];
-          const float p0 = pr[jj], p1 = pr[p1_idx], p2 = pr[p2_idx], p3 = pr[jj & 1];
+          const float p0 = pr[jj], p1 = pr[p1_idx], p2 = pr[p2_idx], p3 = pr[D::R + (jj & 1)];
           const float b0 = p0, b1 = jj == 3 ? p1 - c1 : p1, b2 = p2 - c2, b3 = p3 - c3;
 #pragma unroll
           for (int nt = 0; nt < 2; ++nt) {
@@ -700,24 +759,29 @@ __device__ __forceinline__ void pfn_32_128_tiles(const PfnArgs& a, const float* 
 // 8-wave heavy block made the merged kernel's register budget 128 and the batched path, whose weights alone are 144 registers,
 // lost 6 us to it.)
 static_assert(kHeavyWaves * 64 == 256, "both bodies of dynamic_pfn_32_128_kernel are 256-thread blocks");
+template <int SHAPE>
 __global__ __launch_bounds__(256) void dynamic_pfn_32_128_main_kernel(PfnArgs a, const float* __restrict__ cs_table) {
-  pfn_32_128_main(a, cs_table, blockIdx.x, gridDim.x);
+  pfn_32_128_main<SHAPE>(a, cs_table, blockIdx.x, gridDim.x);
 }
+template <int SHAPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dynamic_pfn_32_128_tile_kernel(PfnArgs a, const float* __restrict__ cs_table) {
-  pfn_32_128_tiles(a, cs_table, blockIdx.x, gridDim.x);
+  pfn_32_128_tiles<SHAPE>(a, cs_table, blockIdx.x, gridDim.x);
 }
 
+template <int SHAPE>
 __global__ __launch_bounds__(256) void dynamic_pfn_32_128_heavy16_kernel(PfnArgs a, const float* __restrict__ cs_table) {
-  pfn_32_128_heavy<kTileRows>(a, cs_table, blockIdx.x, gridDim.x);
+  pfn_32_128_heavy<SHAPE, kTileRows>(a, cs_table, blockIdx.x, gridDim.x);
 }
+template <int SHAPE>
 __global__ __launch_bounds__(256) void dynamic_pfn_32_128_heavy_kernel(PfnArgs a, const float* __restrict__ cs_table) {
-  pfn_32_128_heavy(a, cs_table, blockIdx.x, gridDim.x);
+  pfn_32_128_heavy<SHAPE>(a, cs_table, blockIdx.x, gridDim.x);
 }
+template <int SHAPE>
 __global__ __launch_bounds__(256) void dynamic_pfn_32_128_kernel(PfnArgs a, const float* __restrict__ cs_table, int main_blocks) {
   if ((int)blockIdx.x < main_blocks) {
-    pfn_32_128_main(a, cs_table, blockIdx.x, main_blocks);
+    pfn_32_128_main<SHAPE>(a, cs_table, blockIdx.x, main_blocks);
   } else {
-    pfn_32_128_heavy(a, cs_table, blockIdx.x - main_blocks, gridDim.x - main_blocks);
+    pfn_32_128_heavy<SHAPE>(a, cs_table, blockIdx.x - main_blocks, gridDim.x - main_blocks);
   }
 }
 
@@ -764,10 +828,11 @@ __device__ __forceinline__ float reduce_scatter(float (&v)[N], int lane) {
 constexpr int kBwdBatch = 32;  // pillars staged per block and round
 constexpr int kBwdPts = 4;     // points per pillar staged in LDS (pillars with more read global memory)
 
-template <int C0, int C1>
+template <int C0, int C1, int SHAPE>
 __global__ __launch_bounds__(256) void dynamic_pfn_bwd_kernel(PfnArgs a, const float* __restrict__ cs_table,
                                                               const float* __restrict__ dfeat, const float* __restrict__ dcanvas,
                                                               float* __restrict__ slabs, int slab_waves, int skip_single) {
+  using D = Cols<SHAPE>;
   constexpr int K1 = 2 * C0;             // row length of W1
   constexpr int SLAB = 64 * K1 + C0 * 16;
   constexpr int NB = kBwdBatch, KP = kBwdPts;
@@ -861,14 +926,13 @@ __global__ __launch_bounds__(256) void dynamic_pfn_bwd_kernel(PfnArgs a, const f
       uint32_t key = m_key[q];
       const int ri = key % a.R; key /= a.R;
       const int ti = key % a.T;
-      const float rc = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
-      const float pc = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
-      const float xc = __fmul_rn(rc, cs_table[2 * ti]), yc = __fmul_rn(rc, cs_table[2 * ti + 1]);
+      float rc, pc, xc, yc;
+      pillar_centre<SHAPE>(a, cs_table, ri, ti, rc, pc, xc, yc);
       float mx, my, mz, mr, mp;
       float d[16];
       auto decorate = [&](const float* p) {
-        const float rho = p[0], phi = p[1], z = p[2], x = p[3], y = p[4];
-        const float t[16] = {rho, phi, z, x, y, p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc, rho - mr, phi - mp, rho - rc, phi - pc};
+        const float rho = p[D::R], phi = p[D::P], z = p[D::Z], x = p[D::X], y = p[D::Y];
+        const float t[16] = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], x - mx, y - my, z - mz, x - xc, y - yc, rho - mr, phi - mp, rho - rc, phi - pc};
 #pragma unroll
         for (int k = 0; k < 16; ++k) d[k] = t[k];
       };
@@ -886,7 +950,7 @@ __global__ __launch_bounds__(256) void dynamic_pfn_bwd_kernel(PfnArgs a, const f
         for (int j = 0; j < KP; ++j)
           if (j < n) {
             const float* p = p_l[q][j];
-            sr += to_fix(p[0]); sp += to_fix(p[1]); sz += to_fix(p[2]); sx += to_fix(p[3]); sy += to_fix(p[4]);
+            sr += to_fix(p[D::R]); sp += to_fix(p[D::P]); sz += to_fix(p[D::Z]); sx += to_fix(p[D::X]); sy += to_fix(p[D::Y]);
           }
         const double inv_n = 1.0 / ((double)n * kFix);
         mx = (float)((double)sx * inv_n); my = (float)((double)sy * inv_n); mz = (float)((double)sz * inv_n);
@@ -944,7 +1008,7 @@ __global__ __launch_bounds__(256) void dynamic_pfn_bwd_kernel(PfnArgs a, const f
       long long sx = 0, sy = 0, sz = 0, sr = 0, sp = 0;
       for (int i = s + lane; i < e; i += 64) {
         const float* p = a.pts + (size_t)a.order[i] * a.stride;
-        sr += to_fix(p[0]); sp += to_fix(p[1]); sz += to_fix(p[2]); sx += to_fix(p[3]); sy += to_fix(p[4]);
+        sr += to_fix(p[D::R]); sp += to_fix(p[D::P]); sz += to_fix(p[D::Z]); sx += to_fix(p[D::X]); sy += to_fix(p[D::Y]);
       }
       const double inv_n = 1.0 / ((double)n * kFix);
       mx = (float)((double)pn::wave_sum(sx) * inv_n); my = (float)((double)pn::wave_sum(sy) * inv_n);
@@ -1025,8 +1089,10 @@ constexpr int kS1WsFloats = 128 * kS1H;
 constexpr int kS1Waves = 8;     // two waves per SIMD: a tile's dependent index / point / dY loads hide behind the other wave's MFMAs
 constexpr size_t kS1Smem = (size_t)(kS1WsFloats + kS1Waves * kS1WaveFloats) * sizeof(float);
 
+template <int SHAPE>
 __global__ __launch_bounds__(64 * kS1Waves) void pfn_bwd_single_kernel(PfnArgs a, const float* __restrict__ cs_table, const float* __restrict__ dfeat,
                                                              const float* __restrict__ dcanvas, float* __restrict__ slabs, int slab_waves, int wave_base) {
+  using D = Cols<SHAPE>;
   constexpr int C0 = 32, C1 = 128, K1 = 64, SLAB = 64 * K1 + C0 * 16;
   extern __shared__ __attribute__((aligned(16))) float s1_lds[];
   float* Ws = s1_lds;
@@ -1068,14 +1134,15 @@ __global__ __launch_bounds__(64 * kS1Waves) void pfn_bwd_single_kernel(PfnArgs a
     const int bi = kk_ / a.Z;
     if (one) {
       const float* p = a.pts + (size_t)a.order[s] * a.stride;
-      const float rho = p[0], phi = p[1], z = p[2], x = p[3], y = p[4], p5 = p[5], p6 = p[6];
-      const float rc = __fadd_rn(__fmul_rn((float)ri, a.vx), a.xoff);
-      const float pc = __fadd_rn(__fmul_rn((float)ti, a.vy), a.yoff);
-      const float xc = __fmul_rn(rc, cs_table[2 * ti]), yc = __fmul_rn(rc, cs_table[2 * ti + 1]);
+      const float p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3], p4 = p[4], p5 = p[5], p6 = p[6];
+      const float pv[7] = {p0, p1, p2, p3, p4, p5, p6};
+      const float rho = pv[D::R], phi = pv[D::P], z = pv[D::Z], x = pv[D::X], y = pv[D::Y];
+      float rc, pc, xc, yc;
+      pillar_centre<SHAPE>(a, cs_table, ri, ti, rc, pc, xc, yc);
       const double inv_n = 1.0 / kFix;
       const float mx = (float)((double)to_fix(x) * inv_n), my = (float)((double)to_fix(y) * inv_n), mz = (float)((double)to_fix(z) * inv_n);
       const float mr = (float)((double)to_fix(rho) * inv_n), mp = (float)((double)to_fix(phi) * inv_n);
-      const float t[16] = {rho, phi, z, x, y, p5, p6, x - mx, y - my, z - mz, x - xc, y - yc, rho - mr, phi - mp, rho - rc, phi - pc};
+      const float t[16] = {p0, p1, p2, p3, p4, p5, p6, x - mx, y - my, z - mz, x - xc, y - yc, rho - mr, phi - mp, rho - rc, phi - pc};
 #pragma unroll
       for (int k = 0; k < 16; ++k) d[k] = t[k];
     }
@@ -1251,6 +1318,54 @@ __global__ void clear_canvas_cells_kernel(const uint32_t* __restrict__ ukeys, co
   }
 }
 
+// the launches of the (32, 128) reader for one voxel shape
+template <int SHAPE>
+int launch_pfn_32_128(const PfnArgs& a, const float* center_table, int v_capacity, int tiles, pn_stream_t stream) {
+  const int blocks = std::max(1, std::min(512, pn::cdiv(v_capacity, kFwdBatch)));  // persistent: 2 waves per SIMD, weights loaded once per wave
+  // at most n / kHeavyPillar pillars can be heavy; the blocks find them by scanning voxel_start
+  const int hblocks = std::max(1, std::min(256, pn::cdiv(v_capacity, kHeavyPillar)));
+  // two launches by default: the merged kernel (PN_PFN_SPLIT=0) was measured 7 us SLOWER than main + heavy back to back
+  // (45.3 vs 33.3 + 4.8 us inside a frame) although its register count and LDS are those of the batched path alone
+  if (tiles) {
+    const int hb16 = std::max(1, std::min(512, pn::cdiv(v_capacity, 64)));
+    // (two launches: both bodies in one kernel measured 38 against 28 us at 30 k points and 207 against 137 at 300 k -- as for the r4 pair)
+    hipLaunchKernelGGL(dynamic_pfn_32_128_tile_kernel<SHAPE>, dim3(blocks), dim3(256), 0, pn::S(stream), a, center_table);
+    hipLaunchKernelGGL(dynamic_pfn_32_128_heavy16_kernel<SHAPE>, dim3(hb16), dim3(256), 0, pn::S(stream), a, center_table);
+    return pn::check_launch("dynamic_pfn_32_128_tile_kernel");
+  }
+  static const int split = [] { const char* e = getenv("PN_PFN_SPLIT"); return e ? atoi(e) : 1; }();
+  if (split) {
+    hipLaunchKernelGGL(dynamic_pfn_32_128_main_kernel<SHAPE>, dim3(blocks), dim3(256), 0, pn::S(stream), a, center_table);
+    hipLaunchKernelGGL(dynamic_pfn_32_128_heavy_kernel<SHAPE>, dim3(hblocks), dim3(256), 0, pn::S(stream), a, center_table);
+    return pn::check_launch("dynamic_pfn_32_128_kernel (split)");
+  }
+  hipLaunchKernelGGL(dynamic_pfn_32_128_kernel<SHAPE>, dim3(blocks + hblocks), dim3(kHeavyWaves * 64), 0, pn::S(stream), a, center_table, blocks);
+  return pn::check_launch("dynamic_pfn_32_128_kernel");
+}
+
+constexpr int kPfnBwdBlocks = 256;  // x 2 passes x 4 waves = two waves per SIMD for the (32, 128) reader
+constexpr int kPfnBwdSlabMax = 64 * 64 + 32 * 16;
+constexpr int kPfnBwdSingleBlocks = 256;   // pfn_bwd_single_kernel: one slab pair per block (512 blocks, two per CU: the same 88 us and more slabs to add)
+
+// the launches of the backward for one voxel shape
+template <int SHAPE>
+void launch_pfn_bwd(const PfnArgs& a, const float* center_table, const float* d_features, const float* d_canvas, float* slabs,
+                           int slab_waves, int passes, bool single, pn_stream_t stream) {
+  if (single) {
+    static bool done[64] = {false};
+    if (pn::first_use_on_device(done))
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pfn_bwd_single_kernel<SHAPE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kS1Smem);
+    hipLaunchKernelGGL(pfn_bwd_single_kernel<SHAPE>, dim3(kPfnBwdSingleBlocks), dim3(64 * kS1Waves), kS1Smem, pn::S(stream), a, center_table, d_features, d_canvas, slabs, slab_waves,
+                       kPfnBwdBlocks * 4);
+  }
+  if (a.c0 == 32)
+    hipLaunchKernelGGL((dynamic_pfn_bwd_kernel<32, 128, SHAPE>), dim3(kPfnBwdBlocks, passes), dim3(256), 0, pn::S(stream), a, center_table, d_features, d_canvas, slabs,
+                       slab_waves, (int)single);
+  else
+    hipLaunchKernelGGL((dynamic_pfn_bwd_kernel<16, 32, SHAPE>), dim3(kPfnBwdBlocks, passes), dim3(256), 0, pn::S(stream), a, center_table, d_features, d_canvas, slabs,
+                       slab_waves, 0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1286,12 +1401,17 @@ int pn_hard_voxel_mean_f32(const float* voxels, const int32_t* num_points, int v
   return pn::check_launch("hard_voxel_mean_kernel");
 }
 
-int pn_dynamic_pfn_fwd(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
-                       const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid,
-                       const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset,
-                       float y_offset, float* features, float* canvas, pn_stream_t stream) {
+// every *_shape entry refuses a voxel shape it does not know before anything else
+#define PN_REQUIRE_SHAPE(what) \
+  PN_REQUIRE(voxel_shape == PN_VOXEL_CYLINDER || voxel_shape == PN_VOXEL_CUBOID, what ": voxel_shape must be PN_VOXEL_CYLINDER (0) or PN_VOXEL_CUBOID (1)")
+
+int pn_dynamic_pfn_fwd_shape(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
+                             const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid,
+                             const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset,
+                             float y_offset, int voxel_shape, float* features, float* canvas, pn_stream_t stream) {
+  PN_REQUIRE_SHAPE("dynamic_pfn");
   PN_REQUIRE(points && voxel_start && order && num_voxels && unq_keys && grid && w0 && w1, "dynamic_pfn: null pointer");
-  PN_REQUIRE(point_stride >= 7, "dynamic_pfn: points need 7 features [rho,phi,z,x,y,i,t]");
+  PN_REQUIRE(point_stride >= 7, "dynamic_pfn: points need 7 features [rho,phi,z,x,y,i,t] (cuboid: [x,y,z,i,t,rho,phi])");
   PN_REQUIRE(c0 >= 1 && c0 <= 64 && c1 >= 1 && c1 <= 128, "dynamic_pfn: supports C0 <= 64, C1 <= 128");
   PN_REQUIRE(features || canvas, "dynamic_pfn: no output requested");
   if (v_capacity == 0) return PN_OK;
@@ -1300,12 +1420,24 @@ int pn_dynamic_pfn_fwd(const float* points, int point_stride, const int32_t* vox
   const size_t smem = (size_t)(16 * c0 + 2 * c0 * c1 + kPfnWaves * 64) * sizeof(float);
   static bool attr_done[64] = {false};
   if (pn::first_use_on_device(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dynamic_pfn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((16 * 64 + 2 * 64 * 128 + kPfnWaves * 64) * sizeof(float)));
+    const int max_smem = (int)((16 * 64 + 2 * 64 * 128 + kPfnWaves * 64) * sizeof(float));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dynamic_pfn_kernel<kCylinder>), hipFuncAttributeMaxDynamicSharedMemorySize, max_smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dynamic_pfn_kernel<kCuboid>), hipFuncAttributeMaxDynamicSharedMemorySize, max_smem);
   }
   const int blocks = std::max(1, std::min(1024, pn::cdiv(v_capacity, kPfnWaves * 2)));
-  hipLaunchKernelGGL(dynamic_pfn_kernel, dim3(blocks), dim3(kPfnWaves * 64), smem, pn::S(stream), a);
+  if (voxel_shape == kCuboid)
+    hipLaunchKernelGGL(dynamic_pfn_kernel<kCuboid>, dim3(blocks), dim3(kPfnWaves * 64), smem, pn::S(stream), a);
+  else
+    hipLaunchKernelGGL(dynamic_pfn_kernel<kCylinder>, dim3(blocks), dim3(kPfnWaves * 64), smem, pn::S(stream), a);
   return pn::check_launch("dynamic_pfn_kernel");
+}
+
+int pn_dynamic_pfn_fwd(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
+                       const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid,
+                       const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset,
+                       float y_offset, float* features, float* canvas, pn_stream_t stream) {
+  return pn_dynamic_pfn_fwd_shape(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy,
+                                  x_offset, y_offset, PN_VOXEL_CYLINDER, features, canvas, stream);
 }
 
 size_t pn_pfn_center_table_floats(int t) { return (size_t)2 * t; }
@@ -1316,54 +1448,57 @@ int pn_pfn_center_table_f32(int t, float vy, float y_offset, float* table, pn_st
   return pn::check_launch("center_table_kernel");
 }
 
-// same contract as pn_dynamic_pfn_fwd plus the azimuth table of pn_pfn_center_table_f32; takes the
-// register-resident fast path when (C0, C1) == (32, 128), otherwise falls back to the generic kernel
+// same contract as pn_dynamic_pfn_fwd_shape plus the azimuth table of pn_pfn_center_table_f32 (cylinder; the cuboid reads none); takes
+// the register-resident fast path when (C0, C1) == (32, 128), otherwise falls back to the generic kernel
 static int dynamic_pfn_fwd_table(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
                                  const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid,
                                  const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset,
-                                 const float* center_table, float* features, float* canvas, uint32_t* cell_count, pn_stream_t stream) {
-  if (!(c0 == 32 && c1 == 128 && center_table))
-    return pn_dynamic_pfn_fwd(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy,
-                              x_offset, y_offset, features, canvas, stream);
+                                 const float* center_table, int voxel_shape, float* features, float* canvas, uint32_t* cell_count,
+                                 pn_stream_t stream) {
+  PN_REQUIRE_SHAPE("dynamic_pfn");
+  if (!(c0 == 32 && c1 == 128 && (center_table || voxel_shape == PN_VOXEL_CUBOID)))
+    return pn_dynamic_pfn_fwd_shape(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy,
+                                    x_offset, y_offset, voxel_shape, features, canvas, stream);
   PN_REQUIRE(points && voxel_start && order && num_voxels && unq_keys && grid && w0 && w1, "dynamic_pfn: null pointer");
   PN_REQUIRE(point_stride >= 7 && (features || canvas), "dynamic_pfn: bad arguments");
   if (v_capacity == 0) return PN_OK;
   PfnArgs a{points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid[0], grid[1], grid[2],
             w0, c0, w1, c1, vx, vy, x_offset, y_offset, features, canvas, cell_count};
-  const int blocks = std::max(1, std::min(512, pn::cdiv(v_capacity, kFwdBatch)));  // persistent: 2 waves per SIMD, weights loaded once per wave
-  // at most n / kHeavyPillar pillars can be heavy; the blocks find them by scanning voxel_start
-  const int hblocks = std::max(1, std::min(256, pn::cdiv(v_capacity, kHeavyPillar)));
-  // two launches by default: the merged kernel (PN_PFN_SPLIT=0) was measured 7 us SLOWER than main + heavy back to back
-  // (45.3 vs 33.3 + 4.8 us inside a frame) although its register count and LDS are those of the batched path alone
   // r5 (late): point rows as 16-column MFMA tiles (same bits; PN_PFN_TILES=0: the wave-per-pillar kernel)
   static const int tiles = [] { const char* e = getenv("PN_PFN_TILES"); return e ? atoi(e) : 1; }();
-  if (tiles) {
-    const int hb16 = std::max(1, std::min(512, pn::cdiv(v_capacity, 64)));
-    // (two launches: both bodies in one kernel measured 38 against 28 us at 30 k points and 207 against 137 at 300 k -- as for the r4 pair)
-    hipLaunchKernelGGL(dynamic_pfn_32_128_tile_kernel, dim3(blocks), dim3(256), 0, pn::S(stream), a, center_table);
-    hipLaunchKernelGGL(dynamic_pfn_32_128_heavy16_kernel, dim3(hb16), dim3(256), 0, pn::S(stream), a, center_table);
-    return pn::check_launch("dynamic_pfn_32_128_tile_kernel");
-  }
-  static const int split = [] { const char* e = getenv("PN_PFN_SPLIT"); return e ? atoi(e) : 1; }();
-  if (split) {
-    hipLaunchKernelGGL(dynamic_pfn_32_128_main_kernel, dim3(blocks), dim3(256), 0, pn::S(stream), a, center_table);
-    hipLaunchKernelGGL(dynamic_pfn_32_128_heavy_kernel, dim3(hblocks), dim3(256), 0, pn::S(stream), a, center_table);
-    return pn::check_launch("dynamic_pfn_32_128_kernel (split)");
-  }
-  hipLaunchKernelGGL(dynamic_pfn_32_128_kernel, dim3(blocks + hblocks), dim3(kHeavyWaves * 64), 0, pn::S(stream), a, center_table, blocks);
-  return pn::check_launch("dynamic_pfn_32_128_kernel");
+  return voxel_shape == kCuboid ? launch_pfn_32_128<kCuboid>(a, center_table, v_capacity, tiles, stream)
+                                : launch_pfn_32_128<kCylinder>(a, center_table, v_capacity, tiles, stream);
 }
 
 // r6: the same launch also zeroes the frame index's per-cell counters (pn_voxel_index_fused_*'s cell_count) of the frame's voxels -- the index
 // launches in front are done with them, and a frame engine whose canvas may stay dirty (PointPillars.forward_cart) then needs no
 // pn_clear_frame_cells launch at all.  (32, 128) readers with an azimuth table only.
+int pn_dynamic_pfn_fwd_table_clear_shape(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
+                                         const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid,
+                                         const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset,
+                                         const float* center_table, int voxel_shape, float* features, float* canvas, uint32_t* cell_count,
+                                         pn_stream_t stream) {
+  PN_REQUIRE_SHAPE("dynamic_pfn_fwd_table_clear");
+  PN_REQUIRE(c0 == 32 && c1 == 128 && (center_table || voxel_shape == PN_VOXEL_CUBOID) && cell_count,
+             "dynamic_pfn_fwd_table_clear: the (32, 128) reader with its azimuth table and the cell counters");
+  return dynamic_pfn_fwd_table(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy, x_offset, y_offset,
+                               center_table, voxel_shape, features, canvas, cell_count, stream);
+}
+
 int pn_dynamic_pfn_fwd_table_clear(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
                                    const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid,
                                    const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset,
                                    const float* center_table, float* features, float* canvas, uint32_t* cell_count, pn_stream_t stream) {
-  PN_REQUIRE(c0 == 32 && c1 == 128 && center_table && cell_count, "dynamic_pfn_fwd_table_clear: the (32, 128) reader with its azimuth table and the cell counters");
+  return pn_dynamic_pfn_fwd_table_clear_shape(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy,
+                                              x_offset, y_offset, center_table, PN_VOXEL_CYLINDER, features, canvas, cell_count, stream);
+}
+
+int pn_dynamic_pfn_fwd_table_shape(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
+                                   const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid,
+                                   const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset,
+                                   const float* center_table, int voxel_shape, float* features, float* canvas, pn_stream_t stream) {
   return dynamic_pfn_fwd_table(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy, x_offset, y_offset,
-                               center_table, features, canvas, cell_count, stream);
+                               center_table, voxel_shape, features, canvas, nullptr, stream);
 }
 
 int pn_dynamic_pfn_fwd_table(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
@@ -1371,7 +1506,7 @@ int pn_dynamic_pfn_fwd_table(const float* points, int point_stride, const int32_
                              const float* w0, int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset,
                              const float* center_table, float* features, float* canvas, pn_stream_t stream) {
   return dynamic_pfn_fwd_table(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy, x_offset, y_offset,
-                               center_table, features, canvas, nullptr, stream);
+                               center_table, PN_VOXEL_CYLINDER, features, canvas, nullptr, stream);
 }
 
 int pn_scatter_canvas_fwd(const float* features, const int64_t* unq, const int32_t* num_voxels, int v_capacity, int c,
@@ -1384,19 +1519,18 @@ int pn_scatter_canvas_fwd(const float* features, const int64_t* unq, const int32
   return pn::check_launch("scatter_canvas_kernel");
 }
 
-constexpr int kPfnBwdBlocks = 256;  // x 2 passes x 4 waves = two waves per SIMD for the (32, 128) reader
-constexpr int kPfnBwdSlabMax = 64 * 64 + 32 * 16;
-constexpr int kPfnBwdSingleBlocks = 256;   // pfn_bwd_single_kernel: one slab pair per block (512 blocks, two per CU: the same 88 us and more slabs to add)
 static const int kPfnBwdSingle = [] { const char* e = getenv("PN_PFN_BWD_SINGLE"); return e ? atoi(e) : 1; }();
 
 size_t pn_dynamic_pfn_bwd_workspace_bytes(void) { return (size_t)(kPfnBwdBlocks * 4 + kPfnBwdSingleBlocks) * 2 * kPfnBwdSlabMax * sizeof(float); }
 
-int pn_dynamic_pfn_bwd(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
-                       const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid, const float* w0,
-                       int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset, const float* center_table,
-                       const float* d_features, const float* d_canvas, float* dw0, float* dw1, int accumulate, void* workspace,
-                       size_t workspace_bytes, pn_stream_t stream) {
-  PN_REQUIRE(points && voxel_start && order && num_voxels && unq_keys && grid && w0 && w1 && center_table && dw0 && dw1 && workspace,
+int pn_dynamic_pfn_bwd_shape(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
+                             const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid, const float* w0,
+                             int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset, const float* center_table,
+                             int voxel_shape, const float* d_features, const float* d_canvas, float* dw0, float* dw1, int accumulate,
+                             void* workspace, size_t workspace_bytes, pn_stream_t stream) {
+  PN_REQUIRE_SHAPE("dynamic_pfn_bwd");
+  PN_REQUIRE(points && voxel_start && order && num_voxels && unq_keys && grid && w0 && w1 && (center_table || voxel_shape == PN_VOXEL_CUBOID) &&
+                 dw0 && dw1 && workspace,
              "dynamic_pfn_bwd: null pointer");
   PN_REQUIRE((c0 == 32 && c1 == 128) || (c0 == 16 && c1 == 32),
              "dynamic_pfn_bwd: built for (C0, C1) = (32, 128) (nuScenes reader) and (16, 32) (reduced test model)");
@@ -1408,23 +1542,24 @@ int pn_dynamic_pfn_bwd(const float* points, int point_stride, const int32_t* vox
   const int passes = pn::cdiv(c1, 64);
   const bool single = c0 == 32 && kPfnBwdSingle;
   const int slab_waves = kPfnBwdBlocks * 4 + (single ? kPfnBwdSingleBlocks : 0);
-  if (single) {
-    static bool done[64] = {false};
-    if (pn::first_use_on_device(done))
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pfn_bwd_single_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kS1Smem);
-    hipLaunchKernelGGL(pfn_bwd_single_kernel, dim3(kPfnBwdSingleBlocks), dim3(64 * kS1Waves), kS1Smem, pn::S(stream), a, center_table, d_features, d_canvas, slabs, slab_waves,
-                       kPfnBwdBlocks * 4);
-  }
-  if (c0 == 32)
-    hipLaunchKernelGGL((dynamic_pfn_bwd_kernel<32, 128>), dim3(kPfnBwdBlocks, passes), dim3(256), 0, pn::S(stream), a, center_table, d_features, d_canvas, slabs,
-                       slab_waves, (int)single);
+  if (voxel_shape == kCuboid)
+    launch_pfn_bwd<kCuboid>(a, center_table, d_features, d_canvas, slabs, slab_waves, passes, single, stream);
   else
-    hipLaunchKernelGGL((dynamic_pfn_bwd_kernel<16, 32>), dim3(kPfnBwdBlocks, passes), dim3(256), 0, pn::S(stream), a, center_table, d_features, d_canvas, slabs,
-                       slab_waves, 0);
+    launch_pfn_bwd<kCylinder>(a, center_table, d_features, d_canvas, slabs, slab_waves, passes, single, stream);
   const int outs = c1 * 2 * c0 + c0 * 16;
   hipLaunchKernelGGL(pfn_bwd_reduce_kernel, dim3(pn::cdiv(outs, 64)), dim3(256), 0, pn::S(stream), slabs, slab_waves, passes, c0, c1,
                      dw0, dw1, accumulate);
   return pn::check_launch("dynamic_pfn_bwd");
+}
+
+int pn_dynamic_pfn_bwd(const float* points, int point_stride, const int32_t* voxel_start, const int32_t* order,
+                       const int32_t* num_voxels, int v_capacity, const uint32_t* unq_keys, const int32_t* grid, const float* w0,
+                       int c0, const float* w1, int c1, float vx, float vy, float x_offset, float y_offset, const float* center_table,
+                       const float* d_features, const float* d_canvas, float* dw0, float* dw1, int accumulate, void* workspace,
+                       size_t workspace_bytes, pn_stream_t stream) {
+  return pn_dynamic_pfn_bwd_shape(points, point_stride, voxel_start, order, num_voxels, v_capacity, unq_keys, grid, w0, c0, w1, c1, vx, vy, x_offset,
+                                  y_offset, center_table, PN_VOXEL_CYLINDER, d_features, d_canvas, dw0, dw1, accumulate, workspace, workspace_bytes,
+                                  stream);
 }
 
 }  // extern "C"

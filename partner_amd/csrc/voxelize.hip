@@ -15,20 +15,35 @@ constexpr int kScanItems = 8;  // words per thread
 constexpr int kScanTile = kScanThreads * kScanItems;
 
 // ---------------------------------------------------------------------------- V0
+// rho, phi of one point: the arithmetic of both transform_points branches (utils.py:34-47)
+__device__ __forceinline__ void point_rho_phi(float x, float y, float& rho, float& phi) {
+  // numpy: sqrt(x**2 + y**2) with every fp32 op rounded separately (no FMA contraction)
+  // the fp64 square root rounded once more to fp32 is the correctly rounded fp32 root (53 >= 2*24+2)
+  rho = (float)sqrt((double)__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)));
+  phi = (float)atan2((double)y, (double)x);
+}
+
 __global__ void cart_to_polar_kernel(const float* __restrict__ cart, int n, int f_in, float* __restrict__ polar) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float* p = cart + (size_t)i * f_in;
   float* o = polar + (size_t)i * (f_in + 2);
   const float x = p[0], y = p[1];
-  // numpy: sqrt(x**2 + y**2) with every fp32 op rounded separately (no FMA contraction)
-  // the fp64 square root rounded once more to fp32 is the correctly rounded fp32 root (53 >= 2*24+2)
-  o[0] = (float)sqrt((double)__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)));
-  o[1] = (float)atan2((double)y, (double)x);
+  point_rho_phi(x, y, o[0], o[1]);
   o[2] = p[2];
   o[3] = x;
   o[4] = y;
   for (int k = 3; k < f_in; ++k) o[k + 2] = p[k];
+}
+
+// the cuboid branch (utils.py:45-47): the row keeps its columns, rho and phi are appended
+__global__ void cart_to_cuboid_kernel(const float* __restrict__ cart, int n, int f_in, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* p = cart + (size_t)i * f_in;
+  float* o = out + (size_t)i * (f_in + 2);
+  for (int k = 0; k < f_in; ++k) o[k] = p[k];
+  point_rho_phi(p[0], p[1], o[f_in], o[f_in + 1]);
 }
 
 // ---------------------------------------------------------------------------- V1
@@ -577,6 +592,13 @@ int pn_cart_to_polar_f32(const float* cart, int n, int f_in, float* polar, pn_st
   if (n == 0) return PN_OK;
   hipLaunchKernelGGL(cart_to_polar_kernel, dim3(pn::cdiv(n, 256)), dim3(256), 0, pn::S(stream), cart, n, f_in, polar);
   return pn::check_launch("cart_to_polar_kernel");
+}
+
+int pn_cart_to_cuboid_f32(const float* cart, int n, int f_in, float* out, pn_stream_t stream) {
+  PN_REQUIRE(cart && out && n >= 0 && f_in >= 3, "cart_to_cuboid: bad arguments");
+  if (n == 0) return PN_OK;
+  hipLaunchKernelGGL(cart_to_cuboid_kernel, dim3(pn::cdiv(n, 256)), dim3(256), 0, pn::S(stream), cart, n, f_in, out);
+  return pn::check_launch("cart_to_cuboid_kernel");
 }
 
 int pn_polar_grid_index_f32(const float* points, int point_stride, int n_capacity, const int32_t* sample_offsets,

@@ -85,6 +85,7 @@ SIGNATURES = {
     "pn_last_error": (_I, [C.c_char_p, _SZ]),
     "pn_device_count": (_I, []),
     "pn_cart_to_polar_f32": (_I, [_P, _I, _I, _P, _P]),
+    "pn_cart_to_cuboid_f32": (_I, [_P, _I, _I, _P, _P]),
     "pn_polar_grid_index_f32": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "pn_keys_from_grid_ind": (_I, [_P, _I, _P, _I, _P, _P]),
     "pn_unique_workspace_bytes": (_SZ, [_U64, _I]),
@@ -104,12 +105,16 @@ SIGNATURES = {
     "pn_hard_voxel_mean_f32": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "pn_concat_voxel_segments_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "pn_dynamic_pfn_fwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P]),
+    "pn_dynamic_pfn_fwd_shape": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _I, _P, _P, _P]),
     "pn_pfn_center_table_floats": (_SZ, [_I]),
     "pn_pfn_center_table_f32": (_I, [_I, _F, _F, _P, _P]),
     "pn_dynamic_pfn_fwd_table": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _P]),
     "pn_dynamic_pfn_fwd_table_clear": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "pn_dynamic_pfn_fwd_table_shape": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _I, _P, _P, _P]),
+    "pn_dynamic_pfn_fwd_table_clear_shape": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _I, _P, _P, _P, _P]),
     "pn_dynamic_pfn_bwd_workspace_bytes": (_SZ, []),
     "pn_dynamic_pfn_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
+    "pn_dynamic_pfn_bwd_shape": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _I, _P, _P, _P, _P, _I, _P, _SZ, _P]),
     "pn_static_pfn_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _F, _F, _F, _P, _P]),
     "pn_scatter_canvas_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pn_fill_zero": (_I, [_P, _SZ, _P]),

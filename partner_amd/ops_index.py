@@ -25,6 +25,16 @@ def cart_to_polar(cart: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def cart_to_cuboid(cart: torch.Tensor) -> torch.Tensor:
+    """transform_points(pc, 'cuboid') (utils.py:45-47): (n, f) [x, y, z, rest...] -> (n, f + 2) [x, y, z, rest..., rho, phi]"""
+    hip.require_device(cart)
+    cart = cart.contiguous()
+    n, f = cart.shape
+    out = torch.empty((n, f + 2), dtype=torch.float32, device=cart.device)
+    hip.call("pn_cart_to_cuboid_f32", cart.data_ptr(), n, f, out.data_ptr(), hip.stream())
+    return out
+
+
 @dataclass
 class GridSpec:
     """polar grid of a voxel generator: lo = range[:3], voxel size, grid = (R, T, Z)"""
@@ -284,6 +294,13 @@ def hard_voxel_mean(voxels: torch.Tensor, num_points: torch.Tensor) -> torch.Ten
 
 
 _CENTER_TABLES = {}
+VOXEL_SHAPES = {"cylinder": 0, "cuboid": 1}      # PN_VOXEL_CYLINDER, PN_VOXEL_CUBOID
+
+
+def voxel_shape_id(voxel_shape: str) -> int:
+    if voxel_shape not in VOXEL_SHAPES:
+        raise ValueError(f"voxel_shape must be one of {sorted(VOXEL_SHAPES)}, not {voxel_shape!r}")
+    return VOXEL_SHAPES[voxel_shape]
 
 
 def pfn_center_table(t: int, vy: float, y_offset: float, device) -> torch.Tensor:
@@ -298,24 +315,26 @@ def pfn_center_table(t: int, vy: float, y_offset: float, device) -> torch.Tensor
 
 def dynamic_pfn(points: torch.Tensor, vi: VoxelIndex, w0: torch.Tensor, w1: torch.Tensor, vx: float, vy: float,
                 x_offset: float, y_offset: float, features: Optional[torch.Tensor], canvas: Optional[torch.Tensor],
-                v_cap: Optional[int] = None, clear_index: Optional[FrameIndexState] = None) -> bool:
-    """``clear_index`` (r6): the frame-index state whose per-cell counters the launch zeroes for the frame's voxels on the way (the (32, 128) reader's
+                v_cap: Optional[int] = None, clear_index: Optional[FrameIndexState] = None, voxel_shape: str = "cylinder") -> bool:
+    """``voxel_shape``: the decoration of feature_deco (pillar_encoder.py:338-391), by column index of the rows -- ``"cuboid"`` reads no
+    azimuth table.  ``clear_index`` (r6): the frame-index state whose per-cell counters the launch zeroes for the frame's voxels on the way (the (32, 128) reader's
     kernels; -> True when it did, False when the caller still has to clear them with ``clear_frame_cells``)"""
     hip.require_device(points, w0, w1)
     assert w0.is_contiguous() and w1.is_contiguous() and points.is_contiguous()
     c0, c1 = w0.shape[0], w1.shape[0]
     assert w0.shape[1] == 16 and w1.shape[1] == 2 * c0
     _, _, g = vi.spec.c_arrays()
-    tab = pfn_center_table(vi.spec.grid[1], vy, y_offset, points.device)
+    shape = voxel_shape_id(voxel_shape)
+    tab = pfn_center_table(vi.spec.grid[1], vy, y_offset, points.device) if voxel_shape == "cylinder" else None
     if clear_index is not None and (c0, c1) == (32, 128) and R.pfn_clears_index:
-        hip.call("pn_dynamic_pfn_fwd_table_clear", points.data_ptr(), points.stride(0), vi.voxel_start.data_ptr(), vi.order.data_ptr(),
+        hip.call("pn_dynamic_pfn_fwd_table_clear_shape", points.data_ptr(), points.stride(0), vi.voxel_start.data_ptr(), vi.order.data_ptr(),
                  vi.num_voxels.data_ptr(), vi.n_cap if v_cap is None else v_cap, vi.unq_keys_ptr, g, w0.data_ptr(), c0,
-                 w1.data_ptr(), c1, float(vx), float(vy), float(x_offset), float(y_offset), tab.data_ptr(), hip.ptr(features),
+                 w1.data_ptr(), c1, float(vx), float(vy), float(x_offset), float(y_offset), hip.ptr(tab), shape, hip.ptr(features),
                  hip.ptr(canvas), clear_index.cell_count.data_ptr(), hip.stream())
         return True
-    hip.call("pn_dynamic_pfn_fwd_table", points.data_ptr(), points.stride(0), vi.voxel_start.data_ptr(), vi.order.data_ptr(),
+    hip.call("pn_dynamic_pfn_fwd_table_shape", points.data_ptr(), points.stride(0), vi.voxel_start.data_ptr(), vi.order.data_ptr(),
              vi.num_voxels.data_ptr(), vi.n_cap if v_cap is None else v_cap, vi.unq_keys_ptr, g, w0.data_ptr(), c0,
-             w1.data_ptr(), c1, float(vx), float(vy), float(x_offset), float(y_offset), tab.data_ptr(), hip.ptr(features),
+             w1.data_ptr(), c1, float(vx), float(vy), float(x_offset), float(y_offset), hip.ptr(tab), shape, hip.ptr(features),
              hip.ptr(canvas), hip.stream())
     return False
 

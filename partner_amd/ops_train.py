@@ -14,7 +14,7 @@ from .ops_common import *  # noqa: F401,F403
 from .ops_common import _f32, _workspace  # noqa: F401
 from .routes import R, S  # noqa: F401
 from .ops_conv import ConvLayer, ConvJob  # noqa: F401
-from .ops_index import CenterLossTargets, VoxelIndex, pfn_center_table  # noqa: F401
+from .ops_index import CenterLossTargets, VoxelIndex, pfn_center_table, voxel_shape_id  # noqa: F401
 
 # ------------------------------------------------------------------------------ conv backward (T1)
 def conv_wgrad(x: torch.Tensor, dout: torch.Tensor, kh: int, kw: int, stride=1, pad=0, cin: Optional[int] = None,
@@ -347,12 +347,15 @@ def center_loss_bwd(hm: torch.Tensor, ncls: int, boxes, tg: CenterLossTargets, c
 def dynamic_pfn_bwd(points: torch.Tensor, vi: VoxelIndex, w0: torch.Tensor, w1: torch.Tensor, vx: float, vy: float,
                     x_offset: float, y_offset: float, d_features: Optional[torch.Tensor] = None,
                     d_canvas: Optional[torch.Tensor] = None, dw0: Optional[torch.Tensor] = None,
-                    dw1: Optional[torch.Tensor] = None, accumulate=False, center_table: Optional[torch.Tensor] = None):
-    """weight gradients of the (32,128) DynamicPFNet given d_features (V,128) or the canvas gradient (B,T,R,128)"""
+                    dw1: Optional[torch.Tensor] = None, accumulate=False, center_table: Optional[torch.Tensor] = None,
+                    voxel_shape: str = "cylinder"):
+    """weight gradients of the (32,128) DynamicPFNet given d_features (V,128) or the canvas gradient (B,T,R,128); ``voxel_shape``: the
+    decoration the forward used (``ops.dynamic_pfn``)"""
     hip.require_device(points, w0, w1)
     lib = hip.load()
     dev = points.device
-    if center_table is None:
+    shape = voxel_shape_id(voxel_shape)
+    if center_table is None and voxel_shape == "cylinder":
         center_table = pfn_center_table(vi.spec.grid[1], vy, y_offset, dev)
     if dw0 is None:
         dw0 = torch.empty_like(w0)
@@ -361,9 +364,9 @@ def dynamic_pfn_bwd(points: torch.Tensor, vi: VoxelIndex, w0: torch.Tensor, w1: 
     _, _, g = vi.spec.c_arrays()
     nbytes = lib.pn_dynamic_pfn_bwd_workspace_bytes()
     ws = _workspace(nbytes, dev)
-    hip.call("pn_dynamic_pfn_bwd", points.data_ptr(), points.shape[1], vi.voxel_start.data_ptr(), vi.order.data_ptr(),
+    hip.call("pn_dynamic_pfn_bwd_shape", points.data_ptr(), points.shape[1], vi.voxel_start.data_ptr(), vi.order.data_ptr(),
              vi.num_voxels.data_ptr(), vi.n_cap, vi.unq_keys_ptr, g, w0.data_ptr(), w0.shape[0], w1.data_ptr(), w1.shape[0],
-             float(vx), float(vy), float(x_offset), float(y_offset), center_table.data_ptr(), hip.ptr(d_features), hip.ptr(d_canvas),
+             float(vx), float(vy), float(x_offset), float(y_offset), hip.ptr(center_table), shape, hip.ptr(d_features), hip.ptr(d_canvas),
              dw0.data_ptr(), dw1.data_ptr(), int(accumulate), ws.data_ptr(), nbytes, hip.stream())
     return dw0, dw1
 

@@ -63,10 +63,10 @@ class DynamicPFNet(nn.Module):
     # -- what the fused HIP kernel covers ---------------------------------------------------
     def _check_supported(self):
         full = self.xyz_cluster and self.raz_cluster and self.xy_center and self.ra_center
-        if not (full and self.voxel_shape != "cuboid" and self.num_input == 7 and len(self.pfn_layers) == 2):
+        if not (full and self.voxel_shape in ops.VOXEL_SHAPES and self.num_input == 7 and len(self.pfn_layers) == 2):
             raise NotImplementedError(
-                "DynamicPFNet HIP kernel: only the cylinder grid with the full 16-channel decoration "
-                "(xyz_cluster, raz_cluster, xy_center, ra_center) and two PFN layers is implemented")
+                "DynamicPFNet HIP kernel: only the cylinder and cuboid grids with the full 16-channel decoration "
+                "(xyz_cluster, raz_cluster, xy_center, ra_center), 7 input features and two PFN layers are implemented")
 
     @property
     def out_channels(self) -> int:
@@ -77,10 +77,11 @@ class DynamicPFNet(nn.Module):
         zero on the way (-> True when it did: ops.dynamic_pfn)"""
         self._check_supported()
         return ops.dynamic_pfn(points, vi, self.pfn_layers[0].linear.weight.detach(), self.pfn_layers[1].linear.weight.detach(),
-                               self.vx, self.vy, self.x_offset, self.y_offset, features, canvas, clear_index=clear_index)
+                               self.vx, self.vy, self.x_offset, self.y_offset, features, canvas, clear_index=clear_index,
+                               voxel_shape=self.voxel_shape)
 
     def forward(self, data):
-        """data: dict(points (N,7) f32, grid_ind (N,4) int64 [b,z,theta,r], [batch_size]) ->
+        """data: dict(points (N,7) f32, grid_ind (N,4) int64 [b,z,theta,r] (cuboid grid: [b,z,y,x]), [batch_size]) ->
         (features (V,C) f32, unq (V,4) int64) exactly as pillar_encoder.py:393-406."""
         points, grid_ind = data["points"], data["grid_ind"]
         hip.require_device(points, grid_ind)

@@ -364,7 +364,7 @@ class PolarPillarTrainStep(OptimizerForwards):
             sparse_first.vi = vi
         else:
             hip.call("pn_fill_zero", canvas.data_ptr(), canvas.numel() * 4, hip.stream())
-        ops.dynamic_pfn(points, vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, None, canvas)
+        ops.dynamic_pfn(points, vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, None, canvas, voxel_shape=r.voxel_shape)
         return canvas
 
     def _forward(self, points, sample_offsets, batch, grid_ind, prev_sweep):
@@ -412,7 +412,8 @@ class PolarPillarTrainStep(OptimizerForwards):
         if seg_dlogits is not None:
             self.seg.backward_canvas(seg_dlogits, d_block)      # the seg head's canvas half: d_canvas, or d_features at the pillar rows
         ops.dynamic_pfn_bwd(self.points, self.vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset,
-                            d_features=d_block if sparse else None, d_canvas=None if sparse else d_block, dw0=ps.g[self.w0], dw1=ps.g[self.w1])
+                            d_features=d_block if sparse else None, d_canvas=None if sparse else d_block, dw0=ps.g[self.w0], dw1=ps.g[self.w1],
+                            voxel_shape=r.voxel_shape)
         ps.side.join()
 
     def _bucket_ready(self, k: int) -> None:

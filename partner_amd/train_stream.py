@@ -554,7 +554,7 @@ class PolarStreamTrainStep(PolarPillarTrainStep):
                 if dlogits is not None:
                     seg.backward_canvas(dlogits, d_sec)      # (the canvases of all sectors have one shape: the head's saved one stands for it)
                 ops.dynamic_pfn_bwd(points, vi, ps.p[self.w0], ps.p[self.w1], r.vx, r.vy, r.x_offset, r.y_offset, d_canvas=d_sec, dw0=ps.g[self.w0],
-                                    dw1=ps.g[self.w1], accumulate=s < nsec - 1)
+                                    dw1=ps.g[self.w1], accumulate=s < nsec - 1, voxel_shape=r.voxel_shape)
             ps.side.join()
             self.vi = kept[-1][1]
             if with_seg:
