@@ -1254,6 +1254,22 @@ int pn_split_polar_sectors_f32(const float *points, int n_capacity, int f, const
                                int nsectors, const float *pc_range, const float *voxel_size, const int32_t *grid,
                                float *out_points, int64_t *grid_ind, uint32_t *keys, int32_t *out_offsets,
                                void *workspace, size_t workspace_bytes, pn_stream_t stream);
+/* Voxelization.voxelize_streaming_cart (det3d/datasets/pipelines/voxelization.py:183-303): cuboid points (n, f >= 7)
+ * [x, y, z, ..., rho, phi] (rho, phi in the LAST two columns: transform_points(pc, 'cuboid') / pn_cart_to_cuboid_f32) of `batch` samples
+ * -> the same rows grouped by (sector, sample) in their original order (out_offsets: nsectors*batch + 1 entries).  Sector i takes
+ * -pi + i * 2 pi / nsectors <= phi < -pi + (i + 1) * 2 pi / nsectors, the first open below, the last open above; phi -= i * 2 pi / nsectors
+ * (bounds and shift are float64 scalars, compared with / taken off the float32 column in float64, :230-231, 264-271: phi is the
+ * reference's bit for bit), x = rho cos(phi), y = rho sin(phi) in float32.  grid_ind [b, z, y, x] / keys (both nullable): floor + clip of
+ * the float32 (p - lo) / voxel_size against the sector grid of :215-222 (nsectors >= 4: grid[0] / 2 x grid[1] / 2; >= 2: grid[1] / 2; the
+ * lower corner stays); b is the sample, or with stacked_batch_index the stacked sample sector * batch + b of a collated STROBE example.
+ * index_in_sample (nullable, n int32): each kept row's index in its sample (points_index, :262-268), what key_points_index is cut from
+ * (:295-297).  pc_range (6) / voxel_size (3) / grid (3) are those of the full sweep.  nsectors: 1, 2 or 4. */
+size_t pn_split_cart_sectors_workspace_bytes(int n_capacity, int nsectors, int batch);
+int pn_split_cart_sectors_f32(const float *points, int n_capacity, int f, const int32_t *sample_offsets, int batch,
+                              int nsectors, const float *pc_range, const float *voxel_size, const int32_t *grid,
+                              int stacked_batch_index, float *out_points, int64_t *grid_ind, uint32_t *keys,
+                              int32_t *index_in_sample, int32_t *out_offsets, void *workspace, size_t workspace_bytes,
+                              pn_stream_t stream);
 /* The row concatenations of the context-padding convolutions (ConvContext / ConvBDCP, det3d/models/necks/rpn_context.py:10-44,
  * 98-158: torch.cat / F.pad along the azimuth axis of NCHW maps = whole-row pieces of NHWC maps): output sample k (of n_out <= 64,
  * out_rows rows of w pixels x c channels) = pieces[3k], pieces[3k+1], pieces[3k+2] stacked; a piece is `rows` rows starting at
@@ -1592,6 +1608,30 @@ typedef struct {
 } pn_warp_strip_job;
 int pn_polar_warp_strips_f32(const pn_warp_strip_job *jobs, int njobs, const float *rot2x2, int batch, int nsectors, int pad,
                              float range_lo, float range_hi, float azimuth_lo, float azimuth_hi, pn_stream_t stream);
+
+/* STROBE's spatial memory (det3d/models/detectors/strobe_uber.py:44-110, 162-210), all levels of the neck in one launch (njobs <= 8).
+ * A job names one level: h, w, c = ONE sector's map; the memory map of that level is (batch, H, W, c) with (H, W) = (2h, 2w) for
+ * nsectors = 4, (2h, w) for 2, (h, w) for 1 (get_grids :48-58).  NHWC, c % 4 == 0, 16-byte aligned maps; x / y bounds are test_cfg.pc_range
+ * [0], [3], [1], [4] as float64 (the reference forms its pitches and half-extents in float64 and rounds them once); bilinear, zero
+ * padding, align_corners = False (torch.nn.functional.grid_sample defaults).  `out` is written with its own pixel stride / channel
+ * offset (floats), e.g. the second half of the (.., 2C) map a memory module of RPNUber convolves (the torch.cat of rpn_uber.py:59).
+ *   build (:172-202): in = the level's stacked sector-major maps (nsectors * batch, h, w, c), out = the memory.  Memory cell (m, n):
+ *     p = (x_lo + (x_hi - x_lo) / W * n, y_lo + (y_hi - y_lo) / H * m), q = rot2x2[b] p, then for sector j = 0 .. nsectors - 1 in order
+ *     s = R(2 pi j / nsectors) q with R = [[cos, -sin], [sin, cos]], normalised by the centre and half-extent of the sector-0 region
+ *     (get_center :72-87), sector j's map sampled there, and every channel whose sample is non-zero overwrites the element.  One pass,
+ *     running value in registers.  nsectors = 1: the plain warp of :173-181.  rot2x2: (batch, 2, 2) row-major.
+ *   read (:89-109, 204-208): in = the memory, out = (nsectors * batch, h, w, c) sector-major.  Sector j, cell (m, n): the sector-0 region's
+ *     cell corner g, the memory sampled at R(2 pi j / nsectors) g divided by the full range's half-extent. */
+typedef struct {
+  const float *in;
+  float *out;
+  int32_t h, w, c;
+  int32_t out_pixel_stride, out_channel_offset;
+} pn_cart_memory_job;
+int pn_cart_memory_build_f32(const pn_cart_memory_job *jobs, int njobs, const float *rot2x2, int batch, int nsectors, double x_lo,
+                             double x_hi, double y_lo, double y_hi, pn_stream_t stream);
+int pn_cart_memory_read_f32(const pn_cart_memory_job *jobs, int njobs, int batch, int nsectors, double x_lo, double x_hi,
+                            double y_lo, double y_hi, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * next-4  global augmentation of one training sample, in place on the device: points (n, point_stride >= 3) [x, y, z, ...]

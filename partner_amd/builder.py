@@ -15,6 +15,13 @@ SECOND_STAGE = Registry("second_stage")
 ROI_HEAD = Registry("roi_head")
 
 
+def register_unbuilt(registry, name, why):
+    """the reference's name resolves in ``registry``, and building it raises a NotImplementedError that says what is missing"""
+    def init(self, *args, **kwargs):
+        raise NotImplementedError(f"{name} is not built: {why}")
+    registry.register_module(type(name, (nn.Module,), {"__init__": init, "__doc__": f"not built: {why}"}))
+
+
 def build(cfg, registry, default_args=None):
     if isinstance(cfg, list):
         return nn.Sequential(*[build_from_cfg(c, registry, default_args) for c in cfg])

@@ -2,6 +2,8 @@
 //   pn_split_polar_sectors_f32   Voxelization.voxelize_streaming_polar, det3d/datasets/pipelines/voxelization.py:305-393:
 //                                stable partition of the polar points by (sector, sample), azimuth shifted into the first sector's
 //                                range, x / y recomputed, grid indices against the sector grid
+//   pn_split_cart_sectors_f32    Voxelization.voxelize_streaming_cart, voxelization.py:183-303: the same partition of cuboid points
+//                                [x, y, z, ..., rho, phi] by their azimuth, against the halved Cartesian grid of the first sector
 //   pn_polar_warp_f32 / _strips  the ego-motion warp of the previous sweep's per-layer maps (PolarStreamBDCP): whole maps, or in one launch
 //                                for all layers only the border rows the streaming pass reads
 //   pn_assemble_rows_f32         the row concatenations of the context-padding convolutions ConvContext / ConvBDCP,
@@ -14,30 +16,81 @@ namespace {
 
 constexpr int kT = 256, kItems = 8, kMaxParts = 64;   // parts = sectors * samples
 
-struct SplitArgs {
+__device__ __forceinline__ int cell_idx(float p, float lo, float vs, int g) {
+  float q = (float)((double)__fsub_rn(p, lo) / (double)vs);   // IEEE fp32 quotient (as pn_polar_grid_index_f32)
+  const float hi = (float)(g - 1);
+  q = q < 0.f ? 0.f : q;
+  q = q > hi ? hi : q;
+  return (int)floorf(q);
+}
+
+// what both splits share: the rows, the parts and the three launches below.  A split adds sector_of_row (the sector of an input row) and
+// move_row (the row as its sector keeps it + its [axis0, axis1, z] cell); batch_index is what column 0 of grid_ind / the keys count.
+struct SplitCommon {
   const float* pts; int n_cap; int f; const int32_t* offs; int batch; int nsectors;
-  float min_az, interval;             // fp32, as numpy forms them from the fp32 range array
-  float lo[3], vs[3]; int g[3];       // base range / voxel size, SECTOR grid (theta cells / nsectors)
+  float lo[3], vs[3]; int g[3];       // base range / voxel size, SECTOR grid
   float* out; int64_t* grid_ind; uint32_t* keys; int32_t* out_offs;
   uint32_t* tile; int ntiles;
 };
 
-// sector of an azimuth: i == 0: phi < hi_0; last: phi >= lo_last; else lo_i <= phi < hi_i  (voxelization.py:346-351)
-__device__ __forceinline__ int sector_of(const SplitArgs& a, float phi) {
-  int s = 0;
-  for (int i = 1; i < a.nsectors; ++i)
-    if (phi >= __fadd_rn(a.min_az, __fmul_rn((float)i, a.interval))) s = i;
-  return s;
-}
+struct SplitArgs : SplitCommon {
+  float min_az, interval;             // fp32, as numpy forms them from the fp32 range array
+  // sector of an azimuth: i == 0: phi < hi_0; last: phi >= lo_last; else lo_i <= phi < hi_i  (voxelization.py:346-351)
+  __device__ __forceinline__ int sector_of_row(const float* row) const {
+    int s = 0;
+    for (int i = 1; i < nsectors; ++i)
+      if (row[1] >= __fadd_rn(min_az, __fmul_rn((float)i, interval))) s = i;
+    return s;
+  }
+  __device__ __forceinline__ int batch_index(int s, int b) const { return b; }
+  __device__ __forceinline__ void move_row(const float* src, float* o, int s, int row_in_sample, uint32_t pos, int cell[3]) const {
+    const float shift = __fsub_rn(__fadd_rn(min_az, __fmul_rn((float)s, interval)), min_az);   // cur_pc_range[1] - pc_range[1]
+    const float rho = src[0], phi = __fsub_rn(src[1], shift);
+    o[0] = rho; o[1] = phi; o[2] = src[2];
+    o[3] = __fmul_rn(rho, cosf(phi));
+    o[4] = __fmul_rn(rho, sinf(phi));
+    for (int c2 = 5; c2 < f; ++c2) o[c2] = src[c2];
+    cell[0] = cell_idx(rho, lo[0], vs[0], g[0]); cell[1] = cell_idx(phi, lo[1], vs[1], g[1]); cell[2] = cell_idx(src[2], lo[2], vs[2], g[2]);
+  }
+};
 
-__device__ __forceinline__ int part_of(const SplitArgs& a, int i) {   // -1: past the last sample
+// Voxelization.voxelize_streaming_cart (voxelization.py:183-303): cuboid rows [x, y, z, ..., rho, phi].  The sector bounds and the shift are
+// the float64 scalars of cur_pc_range (:230-231); a float32 azimuth is compared with them, and has the shift taken off it (:271), in float64
+// (NumPy >= 2 promotion: a float64 scalar is not weak), the difference rounded back into the float32 column.
+constexpr int kMaxCartSectors = 4;
+struct CartSplitArgs : SplitCommon {
+  double lo_phi[kMaxCartSectors], shift[kMaxCartSectors];
+  int32_t* index;                     // nullable: the row's index in its sample (points_index, :262-268)
+  int stacked;                        // column 0 of grid_ind: the stacked sample sector * batch + b (the collated STROBE example) or b
+  __device__ __forceinline__ int sector_of_row(const float* row) const {
+    const double phi = (double)row[f - 1];
+    int s = 0;
+    for (int i = 1; i < nsectors; ++i)
+      if (phi >= lo_phi[i]) s = i;
+    return s;
+  }
+  __device__ __forceinline__ int batch_index(int s, int b) const { return stacked ? s * batch + b : b; }
+  __device__ __forceinline__ void move_row(const float* src, float* o, int s, int row_in_sample, uint32_t pos, int cell[3]) const {
+    const float rho = src[f - 2], phi = (float)((double)src[f - 1] - shift[s]);
+    const float x = __fmul_rn(rho, cosf(phi)), y = __fmul_rn(rho, sinf(phi));
+    o[0] = x; o[1] = y;
+    for (int c2 = 2; c2 < f - 1; ++c2) o[c2] = src[c2];
+    o[f - 1] = phi;
+    if (index) index[pos] = row_in_sample;
+    cell[0] = cell_idx(x, lo[0], vs[0], g[0]); cell[1] = cell_idx(y, lo[1], vs[1], g[1]); cell[2] = cell_idx(src[2], lo[2], vs[2], g[2]);
+  }
+};
+
+template <class A>
+__device__ __forceinline__ int part_of(const A& a, int i) {   // -1: past the last sample
   if (i >= min(a.offs[a.batch], a.n_cap)) return -1;
   int b = 0;
   while (b + 1 < a.batch && i >= a.offs[b + 1]) ++b;
-  return sector_of(a, a.pts[(size_t)i * a.f + 1]) * a.batch + b;
+  return a.sector_of_row(a.pts + (size_t)i * a.f) * a.batch + b;
 }
 
-__global__ __launch_bounds__(kT) void split_count_kernel(SplitArgs a) {
+template <class A>
+__global__ __launch_bounds__(kT) void split_count_kernel(A a) {
   const int base = (blockIdx.x * kT + threadIdx.x) * kItems;
   int part[kItems];
   for (int k = 0; k < kItems; ++k) part[k] = base + k < a.n_cap ? part_of(a, base + k) : -1;
@@ -51,7 +104,7 @@ __global__ __launch_bounds__(kT) void split_count_kernel(SplitArgs a) {
   }
 }
 
-__global__ __launch_bounds__(kT) void split_offsets_kernel(SplitArgs a) {
+__global__ __launch_bounds__(kT) void split_offsets_kernel(SplitCommon a) {
   uint32_t carry = 0;
   const int nparts = a.nsectors * a.batch;
   for (int p = 0; p < nparts; ++p) {
@@ -68,15 +121,8 @@ __global__ __launch_bounds__(kT) void split_offsets_kernel(SplitArgs a) {
   if (threadIdx.x == 0) a.out_offs[nparts] = (int32_t)carry;
 }
 
-__device__ __forceinline__ int cell_idx(float p, float lo, float vs, int g) {
-  float q = (float)((double)__fsub_rn(p, lo) / (double)vs);   // IEEE fp32 quotient (as pn_polar_grid_index_f32)
-  const float hi = (float)(g - 1);
-  q = q < 0.f ? 0.f : q;
-  q = q > hi ? hi : q;
-  return (int)floorf(q);
-}
-
-__global__ __launch_bounds__(kT) void split_scatter_kernel(SplitArgs a) {
+template <class A>
+__global__ __launch_bounds__(kT) void split_scatter_kernel(A a) {
   const int base = (blockIdx.x * kT + threadIdx.x) * kItems;
   int part[kItems];
   for (int k = 0; k < kItems; ++k) part[k] = base + k < a.n_cap ? part_of(a, base + k) : -1;
@@ -87,25 +133,28 @@ __global__ __launch_bounds__(kT) void split_scatter_kernel(SplitArgs a) {
     uint32_t tot;
     uint32_t pos = a.tile[(size_t)p * a.ntiles + blockIdx.x] + pn::block_exclusive_scan<kT>(c, &tot);
     const int s = p / a.batch, b = p - s * a.batch;
-    const float shift = __fsub_rn(__fadd_rn(a.min_az, __fmul_rn((float)s, a.interval)), a.min_az);   // cur_pc_range[1] - pc_range[1]
+    const int bi = a.batch_index(s, b);
     for (int k = 0; k < kItems; ++k) {
       if (part[k] != p) continue;
-      const float* src = a.pts + (size_t)(base + k) * a.f;
-      float* o = a.out + (size_t)pos * a.f;
-      const float rho = src[0], phi = __fsub_rn(src[1], shift);
-      o[0] = rho; o[1] = phi; o[2] = src[2];
-      o[3] = __fmul_rn(rho, cosf(phi));
-      o[4] = __fmul_rn(rho, sinf(phi));
-      for (int c2 = 5; c2 < a.f; ++c2) o[c2] = src[c2];
-      const int r = cell_idx(rho, a.lo[0], a.vs[0], a.g[0]), t = cell_idx(phi, a.lo[1], a.vs[1], a.g[1]), z = cell_idx(src[2], a.lo[2], a.vs[2], a.g[2]);
+      int cell[3];
+      a.move_row(a.pts + (size_t)(base + k) * a.f, a.out + (size_t)pos * a.f, s, base + k - a.offs[b], pos, cell);
       if (a.grid_ind) {
         int64_t* gi = a.grid_ind + (size_t)pos * 4;
-        gi[0] = b; gi[1] = z; gi[2] = t; gi[3] = r;
+        gi[0] = bi; gi[1] = cell[2]; gi[2] = cell[1]; gi[3] = cell[0];
       }
-      if (a.keys) a.keys[pos] = (uint32_t)((((size_t)b * a.g[2] + z) * a.g[1] + t) * a.g[0] + r);
+      if (a.keys) a.keys[pos] = (uint32_t)((((size_t)bi * a.g[2] + cell[2]) * a.g[1] + cell[1]) * a.g[0] + cell[0]);
       ++pos;
     }
   }
+}
+
+// the three launches of a split: per-part counts per tile, their exclusive prefix, the stable scatter
+template <class A>
+int launch_split(const A& a, hipStream_t st, const char* what) {
+  hipLaunchKernelGGL(split_count_kernel<A>, dim3(a.ntiles), dim3(kT), 0, st, a);
+  hipLaunchKernelGGL(split_offsets_kernel, dim3(1), dim3(kT), 0, st, static_cast<const SplitCommon&>(a));
+  hipLaunchKernelGGL(split_scatter_kernel<A>, dim3(a.ntiles), dim3(kT), 0, st, a);
+  return pn::check_launch(what);
 }
 
 // ------------------------------------------------------------------------------------------------ row assembly
@@ -274,11 +323,41 @@ int pn_split_polar_sectors_f32(const float* points, int n_capacity, int f, const
   a.out = out_points; a.grid_ind = grid_ind; a.keys = keys; a.out_offs = out_offsets;
   a.tile = static_cast<uint32_t*>(workspace);
   a.ntiles = pn::cdiv(std::max(n_capacity, 1), kT * kItems);
-  hipStream_t st = pn::S(stream);
-  hipLaunchKernelGGL(split_count_kernel, dim3(a.ntiles), dim3(kT), 0, st, a);
-  hipLaunchKernelGGL(split_offsets_kernel, dim3(1), dim3(kT), 0, st, a);
-  hipLaunchKernelGGL(split_scatter_kernel, dim3(a.ntiles), dim3(kT), 0, st, a);
-  return pn::check_launch("split_polar_sectors");
+  return launch_split(a, pn::S(stream), "split_polar_sectors");
+}
+
+size_t pn_split_cart_sectors_workspace_bytes(int n_capacity, int nsectors, int batch) {
+  return pn_split_polar_sectors_workspace_bytes(n_capacity, nsectors, batch);
+}
+
+int pn_split_cart_sectors_f32(const float* points, int n_capacity, int f, const int32_t* sample_offsets, int batch, int nsectors,
+                              const float* pc_range, const float* voxel_size, const int32_t* grid, int stacked_batch_index, float* out_points,
+                              int64_t* grid_ind, uint32_t* keys, int32_t* index_in_sample, int32_t* out_offsets, void* workspace,
+                              size_t workspace_bytes, pn_stream_t stream) {
+  PN_REQUIRE(points && sample_offsets && pc_range && voxel_size && grid && out_points && out_offsets && workspace, "split_cart_sectors: null pointer");
+  PN_REQUIRE(nsectors == 1 || nsectors == 2 || nsectors == 4, "split_cart_sectors: nsectors must be 1, 2 or 4 (the >= 16 rows of voxelization.py:197-214 are not built)");
+  PN_REQUIRE(n_capacity >= 0 && f >= 7 && batch >= 1 && nsectors * batch <= kMaxParts, "split_cart_sectors: bad sizes (f >= 7, sectors * batch <= 64)");
+  if (workspace_bytes < pn_split_cart_sectors_workspace_bytes(n_capacity, nsectors, batch)) return pn::fail(PN_ERR_WORKSPACE, "split_cart_sectors: workspace too small");
+  CartSplitArgs a;
+  a.pts = points; a.n_cap = n_capacity; a.f = f; a.offs = sample_offsets; a.batch = batch; a.nsectors = nsectors;
+  const double pi = 3.141592653589793, interval = 2 * pi / nsectors;      // voxelization.py:192
+  for (int i = 0; i < nsectors; ++i) {
+    a.lo_phi[i] = -pi + i * interval;                                      // cur_pc_range[1], :231
+    a.shift[i] = a.lo_phi[i] + pi;                                         // :271
+  }
+  for (int k = 0; k < 3; ++k) {
+    a.lo[k] = pc_range[k];
+    a.vs[k] = voxel_size[k];
+    a.g[k] = grid[k];
+  }
+  if (nsectors >= 4) a.g[0] /= 2;                                          // :215-222 (the lower corner stays: only the upper bounds move to 0)
+  if (nsectors >= 2) a.g[1] /= 2;
+  PN_REQUIRE(a.g[0] >= 1 && a.g[1] >= 1 && a.g[2] >= 1, "split_cart_sectors: empty sector grid");
+  PN_REQUIRE((uint64_t)batch * nsectors * a.g[0] * a.g[1] * a.g[2] < (1ull << 32), "split_cart_sectors: more than 2^32 cells");
+  a.out = out_points; a.grid_ind = grid_ind; a.keys = keys; a.out_offs = out_offsets; a.index = index_in_sample; a.stacked = stacked_batch_index != 0;
+  a.tile = static_cast<uint32_t*>(workspace);
+  a.ntiles = pn::cdiv(std::max(n_capacity, 1), kT * kItems);
+  return launch_split(a, pn::S(stream), "split_cart_sectors");
 }
 
 int pn_assemble_rows_f32(const pn_row_piece* pieces, int n_out, int out_rows, int w, int c, float* out, int out_pixel_stride,

@@ -734,6 +734,88 @@ class PolarStreamBDCP(PolarStream):
 
 
 @DETECTORS.register_module
+class STROBE(PolarStreamBDCP):
+    """STROBE (det3d/models/detectors/strobe_uber.py:12-276), the Cartesian sector-streaming baseline: ``forward`` takes the LIST of
+    collated sweeps, oldest first, every sweep's sectors stacked in the batch axis (sector-major) on the first sector's Cartesian grid
+    (``ops.split_cart_sectors``).  Every sweep but the last runs ``feature_only``: reader, scatter and the neck (RPNUber), then per level
+    the sectors' maps are rotated and ego-warped into one whole-frame memory (``ops.cart_memory_build`` with that example's
+    ``transform_matrix[:bs]``) and the memory is resampled into every sector's frame (``ops.cart_memory_read``) for the next sweep's
+    memory modules -- two launches per sweep for all levels, the grids of get_grids / get_center computed inside them.  The last sweep
+    runs the heads; its sectors' predictions go through ``CenterHeadSingle.predict`` (``sec_id`` / ``prev_dets`` under
+    test_cfg.stateful_nms) and ``SingleConvHead.predict``, and ``merge_sectors`` puts them together.  Inference in f32 through the host API.
+    The stacked-sweep plumbing -- canvas, per-sector slices, the per-sector predict loop -- is PolarStreamBDCP's; its polar warp, strips and
+    device path are not used (``device_only`` is refused)."""
+
+    def __init__(self, reader, backbone, neck, bbox_head, seg_head=None, part_head=None, train_cfg=None, test_cfg=None, pretrained=None,
+                 nsectors=1):
+        ops.cart_sector_grid((2, 2, 1), int(nsectors))      # refuses the sector counts whose grid tables are not built
+        PolarStream.__init__(self, reader, backbone, neck, bbox_head, seg_head, part_head, train_cfg, test_cfg, pretrained)
+        self.nsectors = int(nsectors)
+
+    def set_compute_dtype(self, dtype: str):
+        if dtype != "f32":
+            raise NotImplementedError("STROBE runs in f32 only: bf16 is not built for the memory modules and the memory kernels")
+        return self
+
+    def _refuse_unbuilt(self, return_loss, **kwargs):
+        eval_only(self, "STROBE")
+        if return_loss:
+            raise NotImplementedError("STROBE: return_loss=True is not built -- training the Cartesian streamer (gradients through the memory "
+                                      "modules) is a follow-up; call forward(example_list, return_loss=False)")
+        if kwargs.get("device_only", False):
+            raise NotImplementedError("STROBE: device_only / graph capture is not built; forward(example_list, return_loss=False) is the host API")
+        if self._test_flag("panoptic"):
+            raise NotImplementedError("STROBE: test_cfg.panoptic (strobe_uber.py:268-273) is not built; 'det' and 'seg' are")
+
+    def _stream_sectors(self, canvas, prev_sweep, bs, mode):
+        """strobe_uber.py:111-122: all sectors of the sweep at once, the previous sweeps' maps in front of blocks i >= 1"""
+        return self.neck.forward_nhwc(canvas, prev_sweep)[0]
+
+    def update_memory(self, cur_sweep, transform, bs):
+        """strobe_uber.py:172-208: per level the stacked sector maps (nsectors * bs, h, w, c) -> the map every sector reads in the next sweep,
+        same shape, through the whole-frame memory.  One sector: the ego warp alone (:173-181)"""
+        pr = self._get("pc_range")
+        rot = torch.as_tensor(transform)[:bs]
+        slots = [self.neck.prev_slot(x.shape, x.device) for x in cur_sweep]
+        if self.nsectors == 1:
+            return ops.cart_memory_build(cur_sweep, rot, bs, 1, pr, outs=slots)
+        return ops.cart_memory_read(ops.cart_memory_build(cur_sweep, rot, bs, self.nsectors, pr), bs, self.nsectors, pr, outs=slots)
+
+    def forward_one_sweep(self, example, mode="feature_only", return_loss=False, **kwargs):
+        self._refuse_unbuilt(return_loss, **kwargs)
+        if mode != "feature_only":
+            return super().forward_one_sweep(example, mode, False, **kwargs)
+        canvas, batch = self._canvas(example)
+        _, cur = self.neck.forward_nhwc(canvas, kwargs.get("prev_sweep"))
+        return self.update_memory(cur, example["transform_matrix"], batch // self.nsectors)
+
+    def forward(self, example, return_loss=True, **kwargs):
+        """example: the list of collated sweeps, oldest first (strobe_uber.py:124-142); a dict is one sweep"""
+        self._refuse_unbuilt(return_loss, **kwargs)
+        sweeps = [example] if isinstance(example, dict) else list(example)
+        prev_sweep = None
+        for ex in sweeps[:-1]:
+            prev_sweep = self.forward_one_sweep(ex, "feature_only", False, prev_sweep=prev_sweep)
+        ex = sweeps[-1]
+        rets = self.forward_one_sweep(ex, "eval", False, **dict(kwargs, prev_sweep=prev_sweep))
+        bs = len(ex["num_points"]) // self.nsectors
+        stateful = self.test_cfg is not None and bool(self._get("stateful_nms", False))
+        out = self.merge_sectors(rets, bs, stateful)
+        if stateful and "det" in out:
+            for det, meta in zip(out["det"], ex.get("metadata", [None] * bs)[:bs]):
+                det["metadata"] = meta
+        return out
+
+
+builder.register_unbuilt(DETECTORS, "STROBEV2", "the sector-by-sector memory of strobe_uber.py:279-477 belongs, with STROBEV3, to the variants around "
+                         "torchgeometry.homography_warp; STROBE is the class the reference's strobe configs name")
+builder.register_unbuilt(DETECTORS, "STROBEV3", "it needs torchgeometry.homography_warp (strobe_uber.py:480-674); STROBE is the class the reference's strobe "
+                         "configs name")
+for _name in ("PointPillarsLSTM", "PointPillarsLSTMV1", "PointPillarsNoLSTM"):
+    builder.register_unbuilt(DETECTORS, _name, "the Han detectors (streaming_waymo.py, configs/nusc/pp/han_method) are outside this build")
+
+
+@DETECTORS.register_module
 class VoxelNet(SingleStageDetector):
     """VoxelNet (voxelnet.py:27-131): reader -> sparse 3-D middle encoder -> RPN -> head, the detector of the reference's
     CenterPoint-style voxel configs (VoxelNetV3 is this plus the re-alignment attention).  Eval mode, on the HIP kernels."""

@@ -42,6 +42,13 @@ class WarpStripJob(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32)]
 
 
+class CartMemoryJob(C.Structure):
+    """mirror of ``pn_cart_memory_job``"""
+
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("out_pixel_stride", C.c_int32),
+                ("out_channel_offset", C.c_int32)]
+
+
 class PanopticSectorJob(C.Structure):
     """mirror of ``pn_panoptic_sector_job``"""
 
@@ -224,6 +231,8 @@ SIGNATURES = {
     "pn_panoptic_box_ids": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
     "pn_split_polar_sectors_workspace_bytes": (_SZ, [_I, _I, _I]),
     "pn_split_polar_sectors_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "pn_split_cart_sectors_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "pn_split_cart_sectors_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "pn_assemble_rows_f32": (_I, [C.POINTER(RowPiece), _I, _I, _I, _I, _P, _I, _I, _P]),
     "pn_sparse_neighbors_transpose": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "pn_sparse_conv_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
@@ -307,6 +316,8 @@ SIGNATURES = {
     "pn_pillar_conv3x3_wgrad_f32": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _SZ, _P]),
     "pn_polar_warp_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P]),
     "pn_polar_warp_strips_f32": (_I, [C.POINTER(WarpStripJob), _I, _P, _I, _I, _I, _F, _F, _F, _F, _P]),
+    "pn_cart_memory_build_f32": (_I, [C.POINTER(CartMemoryJob), _I, _P, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    "pn_cart_memory_read_f32": (_I, [C.POINTER(CartMemoryJob), _I, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "pn_contract_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "pn_softmax_f32": (_I, [_P, _P, C.c_longlong, _I, _I, _P]),
     "pn_softmax_bwd_f32": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P]),

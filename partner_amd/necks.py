@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from . import hip, ops
-from .builder import NECKS
+from .builder import NECKS, register_unbuilt
 from .nn_utils import PlanCache, Sequential, build_norm_layer, eval_only
 
 
@@ -116,9 +116,10 @@ class RPN(nn.Module):
                 plan["deblocks"].append(self._fused(up, bn, up.stride[0], 0, dtype=dtype))
         return plan
 
-    def forward_nhwc(self, x: torch.Tensor, return_blocks=False, pillars=None):
+    def forward_nhwc(self, x: torch.Tensor, return_blocks=False, pillars=None, before_block=None):
         """x: NHWC (B,H,W,C) f32 -> NHWC (B,H',W',sum(us_filters)) f32.  ``pillars``: the frame's ops.VoxelIndex when x is the
-        pillar canvas (its cells are the only non-zero pixels): the first convolution then multiplies (pillar, tap) pairs only"""
+        pillar canvas (its cells are the only non-zero pixels): the first convolution then multiplies (pillar, tap) pairs only.
+        ``before_block(i, x) -> x``: what a subclass puts in front of block i (RPNUber's memory modules); the plan is the same"""
         eval_only(self, "RPN")
         dtype = getattr(self, "compute_dtype", "f32")
         if dtype == "bf16":
@@ -131,6 +132,8 @@ class RPN(nn.Module):
         out, off, block_outs = None, 0, []
         self.canvas_read_by_pillars_only = False      # set below when the first layer took the row-band pillar form (it reads the frame's cells only)
         for i, layers in enumerate(plan["blocks"]):
+            if before_block is not None:
+                x = before_block(i, x)
             for k, layer in enumerate(layers):
                 p0 = plan.get("pillar0") if (i == 0 and k == 0 and pillars is not None and dtype == "f32") else None
                 if p0 is not None and p0.worth_it(pillars, x.shape[0], x.shape[1], x.shape[2]):
@@ -177,3 +180,88 @@ class RPN(nn.Module):
         eval_only(self, "RPN")
         hip.require_device(x)
         return ops.as_nchw(self.forward_nhwc(ops.to_nhwc(x)))
+
+
+@NECKS.register_module
+class RPNUber(RPN):
+    """RPN with STROBE's memory modules (det3d/models/necks/rpn_uber.py:8-69): in front of every block i >= 1 the block's input x is
+    concatenated with the previous sweeps' map of that level and reduced back to its width by ``memory{i}`` = Conv3x3(2C -> 2C, bias),
+    GroupNorm(C, 2C), ReLU, Conv1x1(2C -> C, bias), GroupNorm(C, C), ReLU.  Blocks and deblocks are RPN's plan.  f32, eval mode."""
+
+    def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters, num_input_features, norm_cfg=None,
+                 name="rpn", logger=None, **kwargs):
+        super().__init__(layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters, num_input_features, norm_cfg, name,
+                         logger, **kwargs)
+        cin = [num_input_features, *ds_num_filters[:-1]]
+        for i in range(1, len(layer_nums)):
+            c = cin[i]
+            setattr(self, "memory" + str(i), Sequential(nn.Conv2d(2 * c, 2 * c, 3, padding=1), nn.GroupNorm(c, 2 * c), nn.ReLU(),
+                                                        nn.Conv2d(2 * c, c, 1), nn.GroupNorm(c, c), nn.ReLU()))
+        self._memory_plan = PlanCache()
+
+    def set_compute_dtype(self, dtype: str):
+        if dtype != "f32":
+            raise NotImplementedError("RPNUber runs in f32 only: bf16 memory modules are not built")
+        return super().set_compute_dtype(dtype)
+
+    def _build_memory_plan(self):
+        plan = {}
+        for i in range(1, len(self.blocks)):
+            conv3, gn2, _, conv1, gn1, _ = getattr(self, "memory" + str(i))._modules.values()
+            plan[i] = (ops.ConvLayer(conv3.weight, stride=1, pad=1, shift=conv3.bias), gn2, ops.ConvLayer(conv1.weight, stride=1, pad=0, shift=conv1.bias), gn1)
+        return plan
+
+    @staticmethod
+    def prev_slot(shape, device) -> torch.Tensor:
+        """an (n, h, w, C) map that is the second half of a fresh (n, h, w, 2C) one: whoever produces ``prev_sweeps[i]`` may write it
+        here (``ops.cart_memory_read(..., outs=)``), and the memory module then convolves the wide map without copying this half"""
+        n, h, w, c = shape
+        return torch.empty((n, h, w, 2 * c), dtype=torch.float32, device=device)[..., c:]
+
+    @staticmethod
+    def _wide_of(prev):
+        """the (n, h, w, 2C) map whose second half ``prev`` is (``prev_slot``), or None"""
+        n, h, w, c = prev.shape
+        if prev.stride() != (h * w * 2 * c, w * 2 * c, 2 * c, 1) or prev.storage_offset() % (2 * c) != c:
+            return None
+        return prev.as_strided((n, h, w, 2 * c), prev.stride(), prev.storage_offset() - c)
+
+    def _memory(self, plan, i, x, prev):
+        """rpn_uber.py:59-60 on NHWC maps: x (n, h, w, C) and prev, the previous sweeps' map of the same shape"""
+        n, h, w, c = x.shape
+        conv3, gn2, conv1, gn1 = plan[i]
+        hip.require_device(prev)
+        assert tuple(prev.shape) == tuple(x.shape), f"RPNUber: prev_sweeps[{i - 1}] {tuple(prev.shape)} does not match the block input {tuple(x.shape)}"
+        both = self._wide_of(prev)
+        if both is None:
+            both = self._wide_of(self.prev_slot(x.shape, x.device))
+            ops.assemble_rows([[(prev.contiguous(), k, 0, h)] for k in range(n)], w, c, out=both, out_channel_offset=c)
+        ops.assemble_rows([[(x, k, 0, h)] for k in range(n)], w, c, out=both)
+        y = ops.groupnorm_strat(conv3(both), gn2.num_groups, 1, gn2.weight, gn2.bias, eps=gn2.eps, act=ops.ACT_RELU)
+        return ops.groupnorm_strat(conv1(y), gn1.num_groups, 1, gn1.weight, gn1.bias, eps=gn1.eps, act=ops.ACT_RELU)
+
+    def forward_nhwc(self, x: torch.Tensor, prev_sweeps=None):
+        """x NHWC, prev_sweeps: None or one map per block i >= 1 -> (out NHWC, cur_sweep: the input of every block i >= 1, after its memory
+        module when there are previous sweeps, rpn_uber.py:53-69)"""
+        eval_only(self, "RPNUber")
+        plan = self._memory_plan.get(self, self._build_memory_plan) if prev_sweeps is not None else None
+        cur_sweep = []
+
+        def before_block(i, x):
+            if i > 0:
+                if prev_sweeps is not None:
+                    x = self._memory(plan, i, x, prev_sweeps[i - 1])
+                cur_sweep.append(x)
+            return x
+        return super().forward_nhwc(x, before_block=before_block), cur_sweep
+
+    def forward(self, x, prev_sweeps=None):
+        """logical (B,C,H,W) in / out, as rpn_uber.py:53-69"""
+        eval_only(self, "RPNUber")
+        hip.require_device(x)
+        prev = None if prev_sweeps is None else [ops.to_nhwc(p) for p in prev_sweeps]
+        out, cur = self.forward_nhwc(ops.to_nhwc(x), prev)
+        return ops.as_nchw(out), [ops.as_nchw(c) for c in cur]
+
+
+register_unbuilt(NECKS, "RPNWaymo", "the neck of the Han configs (rpn_waymo.py) is outside this build; RPNUber is the neck of the strobe configs")

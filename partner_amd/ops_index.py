@@ -455,10 +455,120 @@ def split_polar_sectors(points: torch.Tensor, sample_offsets: torch.Tensor, batc
     return out, offs, gi, keys
 
 
-def assemble_rows(samples, w: int, c: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+CART_SECTOR_COUNTS = (1, 2, 4)      # the rows of the reference's grid tables that are built (voxelization.py:215-222, strobe_uber.py:54-58)
+
+
+def cart_sector_grid(grid, nsectors: int):
+    """the first sector's Cartesian grid (voxelization.py:215-222): x and y halved for >= 4 sectors, y for >= 2"""
+    if nsectors not in CART_SECTOR_COUNTS:
+        raise NotImplementedError(f"Cartesian sector streaming: nsectors must be one of {CART_SECTOR_COUNTS}; the >= 16 rows of the reference's grid "
+                                  f"tables are not built (got {nsectors})")
+    g = [int(v) for v in grid]
+    return [g[0] // 2 if nsectors >= 4 else g[0], g[1] // 2 if nsectors >= 2 else g[1], g[2]]
+
+
+def split_cart_sectors(points: torch.Tensor, sample_offsets: torch.Tensor, batch: int, nsectors: int, pc_range, voxel_size,
+                       want_grid_ind=True, want_keys=False, want_index=False, stacked=True):
+    """Voxelization.voxelize_streaming_cart (voxelization.py:183-303) on the device: cuboid points (N, F >= 7) [x, y, z, ..., rho, phi] of
+    ``batch`` samples -> (points grouped by (sector, sample) in their original order, with phi shifted into the first sector and x / y
+    recomputed; part offsets (nsectors * batch + 1,) int32 on the device; grid_ind (N, 4) int64 [b, z, y, x] against the sector grid
+    (``cart_sector_grid``), b the stacked sample sector * batch + b (``stacked``: the collated STROBE example) or the sample; keys; each
+    row's index in its sample (N,) int32 -- ``cart_key_points_index`` cuts ``key_points_index`` from it)"""
+    import numpy as np
+    hip.require_device(points, sample_offsets)
+    lib = hip.load()
+    assert points.dtype == torch.float32 and points.is_contiguous() and sample_offsets.dtype == torch.int32
+    n, f = points.shape
+    rg, vs = np.asarray(pc_range, dtype=np.float32), np.asarray(voxel_size, dtype=np.float32)
+    grid = np.round((rg[3:] - rg[:3]) / vs).astype(np.int64)
+    cart_sector_grid(grid, nsectors)
+    dev = points.device
+    out = torch.empty_like(points)
+    offs = torch.empty((nsectors * batch + 1,), dtype=torch.int32, device=dev)
+    gi = torch.empty((max(n, 1), 4), dtype=torch.int64, device=dev) if want_grid_ind else None
+    keys = torch.empty((max(n, 1),), dtype=torch.int32, device=dev) if want_keys else None
+    index = torch.empty((max(n, 1),), dtype=torch.int32, device=dev) if want_index else None
+    nbytes = lib.pn_split_cart_sectors_workspace_bytes(n, nsectors, batch)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    hip.call("pn_split_cart_sectors_f32", points.data_ptr(), n, f, sample_offsets.data_ptr(), batch, nsectors, (C.c_float * 6)(*rg.tolist()),
+             (C.c_float * 3)(*vs.tolist()), (C.c_int32 * 3)(*[int(g) for g in grid]), int(bool(stacked)), out.data_ptr(), hip.ptr(gi), hip.ptr(keys),
+             hip.ptr(index), offs.data_ptr(), ws.data_ptr(), nbytes, hip.stream())
+    return out, offs, gi, keys, index
+
+
+def cart_key_points_index(index: torch.Tensor, part_offsets, n_key_points=None):
+    """``key_points_index`` of every (sector, sample) part as voxelization.py:295-297 cuts it from ``points_index``: the part's rows of
+    ``split_cart_sectors``' index, those below the sample's ``n_key_points`` (a list per sample of the batch; None: all).  Host path: reads
+    the part offsets back.  -> list of nsectors * batch int64 tensors"""
+    offs = [int(v) for v in (part_offsets.tolist() if torch.is_tensor(part_offsets) else part_offsets)]
+    batch = len(n_key_points) if n_key_points is not None else None
+    out = []
+    for p, (lo, hi) in enumerate(zip(offs[:-1], offs[1:])):
+        idx = index[lo:hi].to(torch.int64)
+        if n_key_points is not None:
+            idx = idx[idx < int(n_key_points[p % batch])]
+        out.append(idx)
+    return out
+
+
+def _cart_memory_jobs(ins, outs, dims):
+    """``outs`` may be channel slices of wider NHWC maps (``wide[..., c0:c0 + c]``): the kernels take a pixel stride"""
+    jobs = (hip.CartMemoryJob * len(ins))()
+    for k, (x, y, (h, w, c)) in enumerate(zip(ins, outs, dims)):
+        hip.require_device(x, y)
+        assert x.dtype == torch.float32 and y.dtype == torch.float32 and x.is_contiguous() and x.shape[3] == c and y.shape[3] == c
+        ps = y.stride(2)
+        assert y.stride(3) == 1 and ps >= c and y.stride(1) == y.shape[2] * ps and y.stride(0) == y.shape[1] * y.shape[2] * ps, \
+            "cart_memory: an output must be a dense NHWC map or a channel slice of one"
+        jobs[k].in_, jobs[k].out, jobs[k].h, jobs[k].w, jobs[k].c = x.data_ptr(), y.data_ptr(), h, w, c
+        jobs[k].out_pixel_stride, jobs[k].out_channel_offset = ps, 0
+    return jobs
+
+
+def _cart_memory_factors(nsectors: int):
+    cart_sector_grid((2, 2, 1), nsectors)
+    return (2 if nsectors >= 2 else 1), (2 if nsectors >= 4 else 1)
+
+
+def cart_memory_build(maps, rot2x2: torch.Tensor, batch: int, nsectors: int, pc_range, outs=None):
+    """STROBE's memory update (strobe_uber.py:172-202) for all levels in ONE launch: ``maps`` = per level the stacked sector-major NHWC map
+    (nsectors * batch, h, w, c), ``rot2x2`` (batch, 2, 2) the ego rotation -> per level the memory (batch, H, W, c), (H, W) = (2h, 2w) /
+    (2h, w) / (h, w) for 4 / 2 / 1 sectors: every sector's map rotated and warped in, a later sector overwriting per element where its
+    sample is non-zero.  ``outs``: maps to write into; each may be a channel slice of a wider map.  ``pc_range``: test_cfg.pc_range"""
+    fy, fx = _cart_memory_factors(nsectors)
+    maps = list(maps)
+    dims = [(int(x.shape[1]), int(x.shape[2]), int(x.shape[3])) for x in maps]
+    assert all(x.shape[0] == nsectors * batch for x in maps)
+    if outs is None:
+        outs = [torch.empty((batch, fy * h, fx * w, c), dtype=torch.float32, device=maps[0].device) for h, w, c in dims]
+    assert all(tuple(y.shape[:3]) == (batch, fy * h, fx * w) for y, (h, w, c) in zip(outs, dims))
+    rot = rot2x2.to(maps[0].device).float().contiguous()
+    assert tuple(rot.shape) == (batch, 2, 2)
+    hip.call("pn_cart_memory_build_f32", _cart_memory_jobs(maps, outs, dims), len(maps), rot.data_ptr(), batch, nsectors,
+             float(pc_range[0]), float(pc_range[3]), float(pc_range[1]), float(pc_range[4]), hip.stream())
+    return list(outs)
+
+
+def cart_memory_read(memories, batch: int, nsectors: int, pc_range, outs=None):
+    """The memory resampled into every sector's frame (strobe_uber.py:89-109, 204-208), all levels in ONE launch: per level (batch, H, W, c)
+    -> (nsectors * batch, h, w, c) sector-major.  ``outs``: maps to write into; each may be a channel slice of a wider map, e.g. the second
+    half of the (.., 2c) map the next sweep's memory module convolves (``RPNUber.prev_slot``: the torch.cat of rpn_uber.py:59 never runs)"""
+    fy, fx = _cart_memory_factors(nsectors)
+    memories = list(memories)
+    assert all(m.shape[0] == batch and m.shape[1] % fy == 0 and m.shape[2] % fx == 0 for m in memories)
+    dims = [(int(m.shape[1]) // fy, int(m.shape[2]) // fx, int(m.shape[3])) for m in memories]
+    if outs is None:
+        outs = [torch.empty((nsectors * batch, h, w, c), dtype=torch.float32, device=memories[0].device) for h, w, c in dims]
+    assert all(tuple(y.shape[:3]) == (nsectors * batch, h, w) for y, (h, w, c) in zip(outs, dims))
+    hip.call("pn_cart_memory_read_f32", _cart_memory_jobs(memories, outs, dims), len(memories), batch, nsectors,
+             float(pc_range[0]), float(pc_range[3]), float(pc_range[1]), float(pc_range[4]), hip.stream())
+    return list(outs)
+
+
+def assemble_rows(samples, w: int, c: int, out: Optional[torch.Tensor] = None, out_channel_offset=0) -> torch.Tensor:
     """``samples``: per output sample a list of up to three row pieces, each ``(None, rows)`` (zeros) or ``(tensor, sample, row0, rows)``
     taken from an NHWC map (B, H, W, C') with C' >= c -- the torch.cat / F.pad along the azimuth axis of rpn_context.py's
-    convolutions.  -> NHWC (len(samples), sum(rows), w, c)"""
+    convolutions.  -> NHWC (len(samples), sum(rows), w, c), or channels [out_channel_offset, + c) of a wider ``out``"""
     n = len(samples)
     rows_out = sum(p[-1] for p in samples[0])
     arr = (hip.RowPiece * (3 * n))()
@@ -478,7 +588,7 @@ def assemble_rows(samples, w: int, c: int, out: Optional[torch.Tensor] = None) -
             e.pixel_stride, e.rows = t.shape[3], rows
     if out is None:
         out = torch.empty((n, rows_out, w, c), dtype=torch.float32, device=dev)
-    hip.call("pn_assemble_rows_f32", arr, n, rows_out, w, c, out.data_ptr(), out.shape[3], 0, hip.stream())
+    hip.call("pn_assemble_rows_f32", arr, n, rows_out, w, c, out.data_ptr(), out.shape[3], out_channel_offset, hip.stream())
     return out
 
 
