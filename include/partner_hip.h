@@ -1154,6 +1154,34 @@ int pn_assign_heatmap_polar_f32(const float *gt_boxes, const int32_t *gt_classes
                                 int64_t *ind, uint8_t *mask, int64_t *cat, float *anno_box,
                                 void *workspace, size_t workspace_bytes, pn_stream_t stream);
 
+/* CenterPoint targets of Cartesian sector streaming (STROBE's training targets), on the device.
+ * Replaces, per (sector, sample):
+ *          the train branch of voxelize_streaming_cart   det3d/datasets/pipelines/voxelization.py:191-193, 229-256
+ *          filter_gt ('cylinder')                        det3d/datasets/pipelines/utils.py:19-24
+ *          rotation_points_single_angle(axis=2)          det3d/core/bbox/box_np_ops.py:182-204
+ *          limit_period(0.5, 2 pi) of assign_centerpoint det3d/datasets/pipelines/preprocess.py:396-401
+ *          AssignLabel.assign_heatmap_cuboid             det3d/datasets/pipelines/preprocess.py:193-250
+ * gt_boxes (B, max_gt, box_cols >= 9) f32 [x,y,z,l,w,h,vx,vy,...,yaw] (the yaw is the LAST column), gt_classes (B, max_gt) 1-based
+ * within the task, num_gt (B) device counts: ONE task's boxes of a sweep.  assign_centerpoint groups a task's boxes by class
+ * (preprocess.py:370-406) before it assigns; the sector filter is stable and commutes with that grouping, so the caller passes the
+ * boxes in that order, as for the polar entry.  pc_range (6), voxel_size (3), grid (3) are HOST arrays of the FULL grid; the sector's
+ * grid halves x and y for 4 sectors and y for 2 (voxelization.py:215-222), the feature map is that divided by out_size_factor.
+ * A box is kept by sector s when its centre's float32 azimuth lies in [-pi + s * 2 pi / n, -pi + (s + 1) * 2 pi / n] (float64 bounds,
+ * BOTH ends inclusive: a box on a border is kept by two sectors, and one at +-pi in float32 by none) and its rho is at most
+ * sqrt(x_lo^2 + y_lo^2); one sector filters too.  Kept boxes are rotated by s * 2 pi / n into the first sector's frame (centre,
+ * velocity, yaw) and take the slots 0, 1, ... of their (sector, sample) in their order; only the first max_objs are used.
+ * Outputs for the nsectors * B stacked samples, sector-major (index = sector * B + b, the order of pn_split_cart_sectors_f32 with
+ * stacked = 1): hm (nsectors * B, classes, fy, fx), ind / cat int64 and mask uint8 (nsectors * B, max_objs), anno_box
+ * (nsectors * B, max_objs, 10) = [dx, dy, z, log l, log w, log h, vx, vy, sin yaw, cos yaw]; all fully overwritten (zeroed on the
+ * stream, the heat map drawn with an order-independent integer maximum).  workspace: pn_assign_heatmap_workspace_bytes(nsectors * B,
+ * max_objs).  Refused: nsectors other than 1, 2, 4; box_cols < 9; a short workspace. */
+int pn_assign_heatmap_cart_sectors_f32(const float *gt_boxes, const int32_t *gt_classes, const int32_t *num_gt,
+                                       int batch, int max_gt, int box_cols, int max_objs, int classes, int nsectors,
+                                       const float *pc_range, const float *voxel_size, const int32_t *grid,
+                                       int out_size_factor, float gaussian_overlap, int min_radius, float *hm,
+                                       int64_t *ind, uint8_t *mask, int64_t *cat, float *anno_box,
+                                       void *workspace, size_t workspace_bytes, pn_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * next-4 (device half)  multi-sweep accumulation for streaming inference (BASELINE configs[4]).
  * Replaces read_sweep / remove_close + the concatenation of LoadPointCloudFromFile

@@ -135,6 +135,130 @@ int pn_assign_heatmap_polar_f32(const float* gt_boxes, const int32_t* gt_classes
 }  // extern "C"
 
 // =================================================================================================
+// CenterPoint targets of Cartesian sector streaming (STROBE): per (sector, sample) the sample's boxes are filtered by the sector's
+// azimuth range, rotated into the first sector's frame and drawn on the sector's Cartesian feature map.
+// Reference: voxelize_streaming_cart (train mode)      det3d/datasets/pipelines/voxelization.py:191-193, 229-256
+//            filter_gt, the 'cylinder' branch           det3d/datasets/pipelines/utils.py:19-24
+//            rotation_points_single_angle(axis=2)       det3d/core/bbox/box_np_ops.py:182-204
+//            limit_period(offset 0.5, period 2 pi)      det3d/datasets/pipelines/preprocess.py:396-401, box_np_ops.py:360-361
+//            AssignLabel.assign_heatmap_cuboid          det3d/datasets/pipelines/preprocess.py:193-250
+// The dtypes are numpy's: the centre's rho and azimuth are float32 and are compared as float64 against the float64 bounds (both azimuth
+// ends inclusive); the centre is rotated with the float32 roundings of the float64 cos / sin, the velocity -- stacked with a float64 zero
+// column by the reference -- in float64; the yaw takes the float64 angle, is rounded to float32 and wrapped in float32.  The per-sector
+// constants are formed on the host, statement by statement as the reference forms them.  One block per (sector, sample): flag -> block
+// scan (fixed order) -> the box's slot is its index among the sector's kept boxes; the heat map is drawn by `draw_gaussian_kernel`.
+// =================================================================================================
+namespace {
+
+constexpr int kCartT = 256, kCartMaxSectors = 4;
+
+struct CartAssignArgs {
+  const float* boxes; const int32_t* classes; const int32_t* num_gt;
+  int B, max_gt, cols, max_objs, fx, fy, osf, min_radius;
+  float vs0, vs1, pc0, pc1, overlap;
+  double r_max, lo[kCartMaxSectors], hi[kCartMaxSectors], angle[kCartMaxSectors], cs[kCartMaxSectors], sn[kCartMaxSectors];
+  int64_t* ind; uint8_t* mask; int64_t* cat; float* anno;
+  int4* draw;  // (nsectors * B, max_objs): x, y, radius, class (-1: nothing to draw)
+};
+
+// grid (nsectors * B): every slot's draw record is written exactly once, by the thread of its box or by the tail loop
+__global__ void __launch_bounds__(kCartT) assign_cart_objects_kernel(CartAssignArgs a) {
+  const int p = blockIdx.x, s = p / a.B, b = p % a.B;
+  const int n = min(max(a.num_gt[b], 0), a.max_gt);
+  const double lo = a.lo[s], hi = a.hi[s], angle = a.angle[s], cs = a.cs[s], sn = a.sn[s];
+  const float cf = (float)cs, sf = (float)sn;
+  uint32_t carry = 0;
+  for (int k0 = 0; k0 < n; k0 += kCartT) {      // (n is the same for the whole block: every thread takes part in the scan)
+    const int k = k0 + threadIdx.x;
+    const float* bx = a.boxes + ((size_t)b * a.max_gt + min(k, n - 1)) * a.cols;
+    const float x = bx[0], y = bx[1];
+    const float rho = fsqrt(x * x + y * y), az = atan2f(y, x);
+    const bool keep = k < n && (double)rho >= 0.0 && (double)rho <= a.r_max && (double)az >= lo && (double)az <= hi;
+    uint32_t tot;
+    const uint32_t slot = carry + pn::block_exclusive_scan<kCartT>(keep ? 1u : 0u, &tot);
+    carry += tot;
+    if (!keep || slot >= (uint32_t)a.max_objs) continue;
+    int4 rec = make_int4(0, 0, 0, -1);
+    const float w = fdiv(fdiv(bx[3], a.vs0), (float)a.osf), l = fdiv(fdiv(bx[4], a.vs1), (float)a.osf);
+    if (w > 0.f && l > 0.f) {
+      const int radius = max(a.min_radius, (int)gaussian_radius_f32(l, w, a.overlap));
+      const float xr = x * cf + y * sf, yr = x * (-sf) + y * cf;
+      const float ctx = fdiv(fdiv(xr - a.pc0, a.vs0), (float)a.osf), cty = fdiv(fdiv(yr - a.pc1, a.vs1), (float)a.osf);
+      const int ix = (int)ctx, iy = (int)cty;      // toward zero, as astype(np.int32)
+      if (ix >= 0 && ix < a.fx && iy >= 0 && iy < a.fy) {
+        const int cls = a.classes[(size_t)b * a.max_gt + k] - 1;
+        rec = make_int4(ix, iy, radius, cls);
+        const double vx = bx[6], vy = bx[7];
+        float yaw = (float)((double)bx[a.cols - 1] + angle);
+        const float period = (float)(2.0 * M_PI);
+        yaw = yaw - floorf(yaw / period + 0.5f) * period;
+        const size_t o = (size_t)p * a.max_objs + slot;
+        a.cat[o] = cls; a.ind[o] = (int64_t)iy * a.fx + ix; a.mask[o] = 1;
+        float* an = a.anno + o * 10;
+        an[0] = ctx - (float)ix; an[1] = cty - (float)iy; an[2] = bx[2];
+        an[3] = logf(bx[3]); an[4] = logf(bx[4]); an[5] = logf(bx[5]);
+        an[6] = (float)(vx * cs + vy * sn); an[7] = (float)(vx * (-sn) + vy * cs); an[8] = sinf(yaw); an[9] = cosf(yaw);
+      }
+    }
+    a.draw[(size_t)p * a.max_objs + slot] = rec;
+  }
+  for (int i = (int)min(carry, (uint32_t)a.max_objs) + threadIdx.x; i < a.max_objs; i += kCartT) a.draw[(size_t)p * a.max_objs + i] = make_int4(0, 0, 0, -1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pn_assign_heatmap_cart_sectors_f32(const float* gt_boxes, const int32_t* gt_classes, const int32_t* num_gt, int batch, int max_gt, int box_cols,
+                                       int max_objs, int classes, int nsectors, const float* pc_range, const float* voxel_size, const int32_t* grid,
+                                       int out_size_factor, float gaussian_overlap, int min_radius, float* hm, int64_t* ind, uint8_t* mask, int64_t* cat,
+                                       float* anno_box, void* workspace, size_t workspace_bytes, pn_stream_t stream) {
+  PN_REQUIRE(gt_boxes && gt_classes && num_gt && pc_range && voxel_size && grid && hm && ind && mask && cat && anno_box && workspace,
+             "assign_heatmap_cart_sectors: null pointer");
+  PN_REQUIRE(nsectors == 1 || nsectors == 2 || nsectors == 4,
+             "assign_heatmap_cart_sectors: nsectors must be 1, 2 or 4 (the >= 16 rows of voxelization.py:197-214 are not built)");
+  PN_REQUIRE(batch >= 1 && max_gt >= 1 && box_cols >= 9 && max_objs >= 1 && classes >= 1 && out_size_factor >= 1,
+             "assign_heatmap_cart_sectors: bad sizes (boxes are [x,y,z,l,w,h,vx,vy,...,yaw] with at least 9 columns)");
+  const int gx = nsectors >= 4 ? grid[0] / 2 : grid[0], gy = nsectors >= 2 ? grid[1] / 2 : grid[1];      // voxelization.py:215-222
+  const int fx = gx / out_size_factor, fy = gy / out_size_factor;
+  PN_REQUIRE(fx >= 1 && fy >= 1, "assign_heatmap_cart_sectors: the sector's feature map is empty");
+  const int samples = nsectors * batch;
+  PN_REQUIRE(workspace_bytes >= pn_assign_heatmap_workspace_bytes(samples, max_objs), "assign_heatmap_cart_sectors: workspace too small");
+  hipStream_t st = pn::S(stream);
+  if (int rc = pn::zero_async(hm, (size_t)samples * classes * fy * fx * 4, st)) return rc;
+  if (int rc = pn::zero_async(ind, (size_t)samples * max_objs * 8, st)) return rc;
+  if (int rc = pn::zero_async(cat, (size_t)samples * max_objs * 8, st)) return rc;
+  if (int rc = pn::zero_async(mask, (size_t)samples * max_objs, st)) return rc;
+  if (int rc = pn::zero_async(anno_box, (size_t)samples * max_objs * 10 * 4, st)) return rc;
+  CartAssignArgs c{};
+  c.boxes = gt_boxes; c.classes = gt_classes; c.num_gt = num_gt;
+  c.B = batch; c.max_gt = max_gt; c.cols = box_cols; c.max_objs = max_objs; c.fx = fx; c.fy = fy; c.osf = out_size_factor; c.min_radius = min_radius;
+  c.vs0 = voxel_size[0]; c.vs1 = voxel_size[1]; c.pc0 = pc_range[0]; c.pc1 = pc_range[1]; c.overlap = gaussian_overlap;
+  // voxelization.py:192-193, 230-231, 245: r from the float32 range, the interval and the bounds in float64, one rounding per operation
+  const float x2 = pc_range[0] * pc_range[0], y2 = pc_range[1] * pc_range[1];
+  const float r2 = x2 + y2;
+  c.r_max = (double)sqrtf(r2);
+  const double two_pi = 2.0 * M_PI;
+  const double interval = two_pi / (double)nsectors;
+  for (int s = 0; s < nsectors; ++s) {
+    const double a0 = (double)s * interval, a1 = (double)(s + 1) * interval;
+    c.lo[s] = -M_PI + a0;
+    c.hi[s] = -M_PI + a1;
+    c.angle[s] = c.lo[s] + M_PI;
+    c.cs[s] = cos(c.angle[s]);
+    c.sn[s] = sin(c.angle[s]);
+  }
+  c.ind = ind; c.mask = mask; c.cat = cat; c.anno = anno_box; c.draw = static_cast<int4*>(workspace);
+  hipLaunchKernelGGL(assign_cart_objects_kernel, dim3(samples), dim3(kCartT), 0, st, c);
+  AssignArgs a{};      // the draw kernel reads B-independent fields only: the record table, the map's size and the class count
+  a.B = samples; a.max_objs = max_objs; a.ncls = classes; a.R = fx; a.A = fy; a.hm = hm; a.draw = c.draw;
+  hipLaunchKernelGGL(draw_gaussian_kernel, dim3(max_objs, samples), dim3(256), 0, st, a);
+  return pn::check_launch("assign_heatmap_cart_sectors");
+}
+
+}  // extern "C"
+
+// =================================================================================================
 // Multi-sweep accumulation on the device (the device half; BASELINE configs[4] "10-sweep
 // accumulation"): raw sweeps (N, 5) f32 [x, y, z, intensity, ring] concatenated key frame first -> (N', 5)
 // [x, y, z, intensity, time lag] in the key frame.

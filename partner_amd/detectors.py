@@ -742,7 +742,8 @@ class STROBE(PolarStreamBDCP):
     ``transform_matrix[:bs]``) and the memory is resampled into every sector's frame (``ops.cart_memory_read``) for the next sweep's
     memory modules -- two launches per sweep for all levels, the grids of get_grids / get_center computed inside them.  The last sweep
     runs the heads; its sectors' predictions go through ``CenterHeadSingle.predict`` (``sec_id`` / ``prev_dets`` under
-    test_cfg.stateful_nms) and ``SingleConvHead.predict``, and ``merge_sectors`` puts them together.  Inference in f32 through the host API.
+    test_cfg.stateful_nms) and ``SingleConvHead.predict``, and ``merge_sectors`` puts them together.  Inference in f32 through the host API;
+    training is ``train_strobe.STROBETrainStep``.
     The stacked-sweep plumbing -- canvas, per-sector slices, the per-sector predict loop -- is PolarStreamBDCP's; its polar warp, strips and
     device path are not used (``device_only`` is refused)."""
 
@@ -760,8 +761,9 @@ class STROBE(PolarStreamBDCP):
     def _refuse_unbuilt(self, return_loss, **kwargs):
         eval_only(self, "STROBE")
         if return_loss:
-            raise NotImplementedError("STROBE: return_loss=True is not built -- training the Cartesian streamer (gradients through the memory "
-                                      "modules) is a follow-up; call forward(example_list, return_loss=False)")
+            raise NotImplementedError("STROBE: return_loss=True is not built on the host API -- training (batch statistics, gradients through "
+                                      "the memory modules, the optimizer) is train_strobe.STROBETrainStep; call forward(example_list, "
+                                      "return_loss=False)")
         if kwargs.get("device_only", False):
             raise NotImplementedError("STROBE: device_only / graph capture is not built; forward(example_list, return_loss=False) is the host API")
         if self._test_flag("panoptic"):

@@ -496,6 +496,41 @@ def split_cart_sectors(points: torch.Tensor, sample_offsets: torch.Tensor, batch
     return out, offs, gi, keys, index
 
 
+def assign_heatmap_cart_sectors(gt_boxes: torch.Tensor, gt_classes: torch.Tensor, num_gt: torch.Tensor, classes: int, max_objs: int, nsectors: int,
+                                pc_range, voxel_size, out_size_factor: int, gaussian_overlap=0.1, min_radius=2) -> CenterLossTargets:
+    """STROBE's training targets on the device: the train branch of voxelize_streaming_cart (voxelization.py:229-256) followed by
+    AssignLabel.assign_heatmap_cuboid (preprocess.py:193-250) for every (sector, sample).  gt_boxes (B, max_gt, cols >= 9) f32
+    [x, y, z, l, w, h, vx, vy, ..., yaw], gt_classes (B, max_gt) int32 (1-based within the task), num_gt (B) int32, all on the device: one
+    task's boxes of a sweep, grouped by class as assign_centerpoint groups them.  ``pc_range`` / ``voxel_size``: the FULL grid's.
+    -> CenterLossTargets for the nsectors * B stacked samples, sector-major (the order of ``split_cart_sectors(stacked=True)``), ``hm``
+    (nsectors * B, classes, fy, fx) on the sector's feature map (``cart_sector_grid`` // out_size_factor)"""
+    import numpy as np
+    hip.require_device(gt_boxes, gt_classes, num_gt)
+    lib = hip.load()
+    assert gt_boxes.dtype == torch.float32 and gt_classes.dtype == torch.int32 and num_gt.dtype == torch.int32
+    assert gt_boxes.dim() == 3 and gt_boxes.is_contiguous() and gt_classes.is_contiguous() and num_gt.is_contiguous()
+    b, max_gt, cols = gt_boxes.shape
+    assert tuple(gt_classes.shape) == (b, max_gt) and num_gt.numel() == b
+    rg, vs = np.asarray(pc_range, dtype=np.float32), np.asarray(voxel_size, dtype=np.float32)
+    grid = np.round((rg[3:] - rg[:3]) / vs).astype(np.int64)
+    gx, gy, _ = cart_sector_grid(grid, nsectors)
+    fx, fy = gx // int(out_size_factor), gy // int(out_size_factor)
+    dev, n = gt_boxes.device, nsectors * b
+    t = CenterLossTargets.__new__(CenterLossTargets)
+    t.hm = torch.empty((n, classes, fy, fx), dtype=torch.float32, device=dev)
+    t.ind = torch.empty((n, max_objs), dtype=torch.int64, device=dev)
+    t.mask = torch.empty((n, max_objs), dtype=torch.uint8, device=dev)
+    t.cat = torch.empty((n, max_objs), dtype=torch.int64, device=dev)
+    t.anno = torch.empty((n, max_objs, 10), dtype=torch.float32, device=dev)
+    nbytes = lib.pn_assign_heatmap_workspace_bytes(n, max_objs)
+    ws = _workspace(nbytes, dev)
+    hip.call("pn_assign_heatmap_cart_sectors_f32", gt_boxes.data_ptr(), gt_classes.data_ptr(), num_gt.data_ptr(), b, max_gt, cols, max_objs, classes,
+             int(nsectors), (C.c_float * 6)(*rg.tolist()), (C.c_float * 3)(*vs.tolist()), (C.c_int32 * 3)(*[int(g) for g in grid]), int(out_size_factor),
+             float(gaussian_overlap), int(min_radius), t.hm.data_ptr(), t.ind.data_ptr(), t.mask.data_ptr(), t.cat.data_ptr(), t.anno.data_ptr(),
+             ws.data_ptr(), nbytes, hip.stream())
+    return t
+
+
 def cart_key_points_index(index: torch.Tensor, part_offsets, n_key_points=None):
     """``key_points_index`` of every (sector, sample) part as voxelization.py:295-297 cuts it from ``points_index``: the part's rows of
     ``split_cart_sectors``' index, those below the sample's ``n_key_points`` (a list per sample of the batch; None: all).  Host path: reads

@@ -13,7 +13,7 @@ CenterHeadSinglePos  and one fused clip + decoupled-weight-decay + Adam update o
 parameter buffer.  All arithmetic runs in kernels of libpartner_hip; PyTorch allocates tensors and
 (for world_size > 1) all-reduces the flat gradient buffer through torch.distributed (RCCL).
 
-The step is made of parts: ``ParamStore`` (the flat buffers), a neck part (``RpnTrain`` here, ``train_stream.ContextNeckTrain`` / ``TrailingEdgeNeckTrain``), the head
+The step is made of parts: ``ParamStore`` (the flat buffers), a neck part (``RpnTrain`` here, ``train_stream.ContextNeckTrain`` / ``TrailingEdgeNeckTrain``, ``train_strobe.UberNeckTrain``), the head
 part (``train_head.CenterHeadTrain``), the seg head (``seg_heads.SegHeadTrain``) and ``FlatAdam`` (schedule, clip, Adam, checkpoint); the
 layer wrappers they are built from are in ``train_layers``.
 
@@ -201,6 +201,28 @@ class OptimizerForwards:
         self.opt.load_state_dict(state)
 
 
+def flat_order_key(up0: int):
+    """-> ``order_key(name)``, the position of a parameter in the step's flat buffer = the reverse of the order in which backward completes
+    the gradients: reader | block 0 (+ its deblock) | memory 1 | block 1 (+ its deblock) | ... | seg head | bbox head.  ``up0``: the neck's
+    first block with a deblock.  RPNUber's ``neck.memory{i}`` sits in front of block i: its backward runs behind block i's and before
+    block i - 1's (and that block's deblock), so its gradients are queued before ``block_done(i - 1)``.  Models without memory modules
+    keep the order they had."""
+
+    def order_key(name: str):
+        parts = name.split(".")
+        if parts[0] == "reader":
+            return 0
+        if parts[0] == "neck" and parts[1] == "blocks":
+            return 1 + 2 * int(parts[2])
+        if parts[0] == "neck" and parts[1] == "deblocks":
+            return 2 + 2 * (int(parts[2]) + up0)
+        if parts[0] == "neck" and parts[1].startswith("memory") and parts[1][6:].isdigit():
+            return 2 * int(parts[1][6:]) + 0.5
+        return 1000 if parts[0] == "bbox_head" else 999
+
+    return order_key
+
+
 class RpnTrain:
     """The RPN (det3d/models/necks/rpn.py:144-159) in training form over a ``ParamStore``: a neck part of the step.
       ``forward(canvas, nsectors, **sweep)`` -> the concatenated deblock outputs (this neck: one sector, no sweep arguments)
@@ -300,18 +322,7 @@ class PolarPillarTrainStep(OptimizerForwards):
         self.dev = dev
         # flat-buffer order = reverse of the order in which backward completes the gradients: reader | block 0 (+ its deblock)
         # | block 1 ... | head, so that the buckets of the gradient exchange (head first) are contiguous ranges
-        up0 = neck._upsample_start_idx
-
-        def order_key(name: str):
-            parts = name.split(".")
-            if parts[0] == "reader":
-                return 0
-            if parts[0] == "neck" and parts[1] == "blocks":
-                return 1 + 2 * int(parts[2])
-            if parts[0] == "neck" and parts[1] == "deblocks":
-                return 2 + 2 * (int(parts[2]) + up0)
-            return 1000 if parts[0] == "bbox_head" else 999
-
+        order_key = flat_order_key(neck._upsample_start_idx)
         self.ps = ps = ParamStore(model, dev, order_key)
         # gradient buckets [lo, hi) in the order backward completes them: the head, the last RPN block (+ deblock), the rest
         first_head = min((ps.offsets[n][0] for n in ps.names if n.startswith("bbox_head.")), default=ps.total)

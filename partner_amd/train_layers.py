@@ -215,13 +215,15 @@ class _ConvReLU:
 
 
 class _ConvGNReLU:
-    """Conv2d(bias) + GroupNorm-family + ReLU (+ calibration second output) of the merged heads"""
+    """Conv2d(bias) + GroupNorm-family + ReLU (+ calibration second output) of the merged heads and of RPNUber's memory modules.  ``pad``:
+    the convolution's padding (its kernel is the weight's: 3x3 / pad 1 in the heads, also 1x1 / pad 0 in the memory modules)"""
 
-    def __init__(self, ps, wname, bname, gname, bename, cgroups, strata, eps, groups=1):
+    def __init__(self, ps, wname, bname, gname, bename, cgroups, strata, eps, groups=1, pad=1):
         self.ps = ps
         self.cgroups, self.strata, self.eps = cgroups, strata, eps
         self.gname, self.bename = gname, bename
-        self.conv = _Conv(ps, wname, bname, 1, 1) if groups == 1 else _GroupedConv(ps, wname, bname, groups)
+        assert groups == 1 or pad == 1, "the grouped convolution is 3x3 / pad 1"
+        self.conv = _Conv(ps, wname, bname, 1, pad) if groups == 1 else _GroupedConv(ps, wname, bname, groups)
         self.y = None
 
     def fwd(self, x, mul=None, add=None):
@@ -231,12 +233,15 @@ class _ConvGNReLU:
         return ops.groupnorm_strat(self.y, self.cgroups, self.strata, self.ps.p[self.gname], self.ps.p[self.bename], self.eps,
                                    act=RELU, mul=mul, add=add, stat_out=self.stat)
 
-    def bwd(self, dout, dout2=None, dx=None, accumulate=False):
-        """-> (dx,) or, with ``dout2`` (the gradient of the calibrated second output), (dx, dmul, dadd)"""
+    def bwd(self, dout, dout2=None, dx=None, accumulate=False, need_dx=True):
+        """-> (dx,) or, with ``dout2`` (the gradient of the calibrated second output), (dx, dmul, dadd).  ``need_dx=False`` (ungrouped): the
+        parameter gradients only; ``dout`` then holds the convolution's output gradient and dx is None"""
         res = ops.groupnorm_strat_bwd(self.y, dout, self.cgroups, self.strata, self.ps.p[self.gname], self.ps.p[self.bename], self.eps,
                                       RELU, dout2=dout2, mul=self.mul if dout2 is not None else None, dx=dout,
                                       dgamma=self.ps.g[self.gname], dbeta=self.ps.g[self.bename], stat=self.stat)
         extra = res[3:] if dout2 is not None else ()
+        if not need_dx:
+            return (self.conv.bwd(res[0], need_dx=False),) + tuple(extra)
         return (self.conv.bwd(res[0], dx=dx, accumulate=accumulate),) + tuple(extra)
 
 
