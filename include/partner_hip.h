@@ -1662,6 +1662,47 @@ int pn_cart_memory_read_f32(const pn_cart_memory_job *jobs, int njobs, int batch
                             double y_lo, double y_hi, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The CenterPoint second stage (det3d/models/detectors/two_stage.py, inference) around the RoIHead's GEMMs: two launches, no
+ * atomics, no LDS, nothing read back.  code_size = 7 | 9 is the RoIHead's; max_rois = NMS_POST_MAXSIZE.
+ *
+ * pn_roi_bev_gather_f32 replaces, in one launch, det3d/models/detectors/two_stage.py:49-76 (get_box_center, with
+ * center_to_corner_box2d / rotation_2d of det3d/core/bbox/box_torch_ops.py:145-203), det3d/models/second_stage/bird_eye_view.py:18-41
+ * with det3d/core/utils/center_utils.py:93-122 (bilinear_interpolate_torch) and two_stage.py:78-119
+ * (reorder_first_stage_pred_and_feature).
+ *   in   the first stage's device list (CenterHead.predict(device_only)): boxes (batch, cap_in, box_cols), scores (batch, cap_in),
+ *        labels (batch, cap_in) int64, counts (batch) int32; rows at or past counts[b] are never read.  bev: the NHWC map
+ *        (batch, h, w, c) with `pixel_stride` floats from pixel to pixel (c % 4 == 0, stride % 4 == 0, 16-byte aligned).
+ *        pc_start[2], voxel_size[2]: HOST arrays (x, y); cell = (a - pc_start) / voxel_size / out_stride, two divisions in fp32.
+ *   out  rois (batch, max_rois, code_size) -- code_size 9: the head's [x, y, z, w, l, h, vx, vy, rot] in the order
+ *        [0, 1, 2, 3, 4, 5, 8, 6, 7] --, roi_scores (batch, max_rois), roi_labels (batch, max_rois) int64 = label + 1, roi_features
+ *        (batch, max_rois, feature_stride >= num_point * c): per ROI the points centre, front, back, left, right (num_point = 5; the
+ *        centre alone for 1), each point's c channels side by side.  Every slot at or past counts[b] is written as zeros (label 0).
+ *   The sample is bilinear_interpolate_torch's: floor, the four indices clamped to the map, the weights formed from the CLAMPED
+ *   indices -- left of column 0, at or right of column w - 1, above row 0 or at or below row h - 1 the same pixel meets two opposite
+ *   weights.  The rotation is the LAST box column, the dims columns 3:5.
+ * PN_ERR_INVALID without a launch: null pointers, num_point not 1 or 5, code_size not 7 or 9, box_cols != code_size, c % 4 != 0,
+ * max_rois < cap_in (the reference's copy into its NMS_POST_MAXSIZE rows fails there too), strides that do not fit.
+ *
+ * pn_roi_refine_f32 replaces det3d/models/roi_heads/roi_head_template.py:153-183 (generate_predicted_boxes) and
+ * det3d/models/detectors/two_stage.py:121-151 (post_process) in one launch.
+ *   in   the gather's rois / roi_scores / roi_labels and the first stage's counts; the RoIHead's raw outputs as row pointers with a
+ *        row stride and a column offset (floats): rcnn_cls (1 column) and rcnn_reg (code_size columns) may be slices of one GEMM output.
+ *   out  a device list in the first stage's format: boxes (batch, max_rois, code_size) = (reg + roi with its xyz zeroed) rotated about z by
+ *        roi[6] (rotate_points_along_z, box_torch_ops.py:124-142) + the roi's xyz, code_size 9 back in the head's order
+ *        [0, 1, 2, 3, 4, 5, 7, 8, 6]; scores = sqrt(sigmoid(cls) * roi_score); labels int64 = roi_label - 1; counts pass through (the
+ *        reference's mask label != 0 keeps exactly the first counts[b] rows).  Rows at or past counts[b] are written as zeros.
+ * PN_ERR_INVALID without a launch: null pointers, code_size not 7 or 9, columns that do not fit their row stride. */
+int pn_roi_bev_gather_f32(const float *boxes, const float *scores, const int64_t *labels, const int32_t *counts, int batch,
+                          int cap_in, int box_cols, const float *bev, int h, int w, int c, int pixel_stride,
+                          const float *pc_start, const float *voxel_size, int out_stride, int num_point, int code_size,
+                          int max_rois, float *rois, float *roi_scores, int64_t *roi_labels, float *roi_features,
+                          int feature_stride, pn_stream_t stream);
+int pn_roi_refine_f32(const float *rois, const float *roi_scores, const int64_t *roi_labels, const int32_t *counts, int batch,
+                      int max_rois, int code_size, const float *rcnn_cls, int cls_stride, int cls_col, const float *rcnn_reg,
+                      int reg_stride, int reg_col, float *out_boxes, float *out_scores, int64_t *out_labels,
+                      int32_t *out_counts, pn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * next-4  global augmentation of one training sample, in place on the device: points (n, point_stride >= 3) [x, y, z, ...]
  * and boxes (m, box_cols = 7 | 9) [x, y, z, w, l, h, (vx, vy,) heading].  Order and arithmetic of
  * prep.random_flip_both / global_rotation / global_scaling_v2 / global_translate_

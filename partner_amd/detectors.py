@@ -52,6 +52,15 @@ class SingleStageDetector(nn.Module):
         self.load_state_dict({k[7:] if k.startswith("module.") else k: v for k, v in sd.items()}, strict=False)
 
 
+def first_stage_device_list(det, example, preds, return_loss, **kwargs):
+    """``forward_two_stage``'s tail: decode + NMS of the first stage's head maps into its fixed-capacity device list"""
+    if return_loss:
+        raise NotImplementedError(f"{type(det).__name__}.forward_two_stage: return_loss=True is not built (the second stage runs inference only)")
+    if det.test_cfg is None:
+        raise ValueError(f"{type(det).__name__}.forward_two_stage needs the detector's test_cfg (build_detector(cfg, test_cfg=...))")
+    return det.bbox_head.predict(example, preds, det.test_cfg, device_only=True, **kwargs)
+
+
 @DETECTORS.register_module
 class PointPillars(SingleStageDetector):
     def __init__(self, reader, backbone, neck, bbox_head, seg_head=None, part_head=None, train_cfg=None, test_cfg=None,
@@ -190,6 +199,10 @@ class PointPillars(SingleStageDetector):
 
     def extract_preds(self, example) -> Dict[str, object]:
         """reference ``example`` dict (dynamic branch keys) -> {'det_preds': [...]}"""
+        return self._heads(*self._neck_maps(example))
+
+    def _neck_maps(self, example):
+        """reference ``example`` dict -> (the NHWC canvas, the NHWC neck output)"""
         eval_only(self, "PointPillars")
         if "voxels" in example:   # hard-voxel (static) branch, point_pillars.py:27-38 / 60-76
             voxels, coords = example["voxels"], example["coordinates"]
@@ -198,7 +211,7 @@ class PointPillars(SingleStageDetector):
             x1 = self.backbone(feats, coords, len(example["num_voxels"]), [int(v) for v in example["shape"][0]])
             x1h = ops.to_nhwc(x1)
             x2 = self.neck.forward_nhwc(x1h) if self.with_neck else x1h
-            return self._heads(x1h, x2)
+            return x1h, x2
         points, grid_ind = example["points"], example["grid_ind"]
         hip.require_device(points, grid_ind)
         batch = len(example["num_points"])
@@ -209,7 +222,13 @@ class PointPillars(SingleStageDetector):
         keys = ops.keys_from_grid_ind(grid_ind.to(torch.int64).contiguous(), spec, batch)
         canvas, vi = self.encode_canvas(points.contiguous(), keys, spec, batch, return_index=True)
         x2 = self._neck_on_canvas(canvas, vi)
-        return self._heads(canvas, x2)
+        return canvas, x2
+
+    def forward_two_stage(self, example, return_loss=False, **kwargs):
+        """the first stage of a TwoStageDetector (point_pillars.py:112-140, two_stage.py:155-166), inference: whatever ``extract_preds``
+        accepts -> (the device list of ``bbox_head.predict(device_only=True)``, the NHWC neck output); nothing is read back"""
+        x1h, x2 = self._neck_maps(example)
+        return first_stage_device_list(self, example, self._heads(x1h, x2), return_loss, **kwargs), x2
 
     def _heads(self, x1_nhwc: torch.Tensor, x2_nhwc: torch.Tensor) -> Dict[str, object]:
         """point_pillars.py:91-96: the detection head on the RPN output, the segmentation head (when the config has one) on the
@@ -838,7 +857,8 @@ class VoxelNet(SingleStageDetector):
         x = self.backbone.forward_nhwc(feats, unq.to(torch.int32), data["batch_size"], [int(v) for v in data["grid_size"]])
         return self.neck.forward_nhwc(x) if self.with_neck else x
 
-    def forward(self, example, return_loss=True, **kwargs):
+    def _neck_map(self, example):
+        """reference ``example`` dict (hard-voxel or dynamic keys) -> the NHWC neck output"""
         eval_only(self, "VoxelNet")
         if "voxels" in example:
             hip.require_device(example["voxels"], example["coordinates"])
@@ -851,7 +871,16 @@ class VoxelNet(SingleStageDetector):
                         batch_size=len(example["num_points"]), voxel_size=example["voxel_size"][0], pc_range=example["pc_range"][0],
                         grid_size=example["grid_size"][0])
             x = self.extract_feat_dynamic(data)
-        preds = self.bbox_head(ops.as_nchw(x))
+        return x
+
+    def forward_two_stage(self, example, return_loss=False, **kwargs):
+        """the first stage of a TwoStageDetector (voxelnet.py:133-168, two_stage.py:155-166), inference: whatever ``forward`` accepts ->
+        (the device list of ``bbox_head.predict(device_only=True)``, the NHWC neck output); nothing is read back"""
+        x = self._neck_map(example)
+        return first_stage_device_list(self, example, self.bbox_head(ops.as_nchw(x)), return_loss, **kwargs), x
+
+    def forward(self, example, return_loss=True, **kwargs):
+        preds = self.bbox_head(ops.as_nchw(self._neck_map(example)))
         if return_loss:
             return self.bbox_head.loss(example, preds)
         if kwargs.get("raw_preds", False) or self.test_cfg is None:

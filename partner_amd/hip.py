@@ -319,6 +319,8 @@ SIGNATURES = {
     "pn_polar_warp_strips_f32": (_I, [C.POINTER(WarpStripJob), _I, _P, _I, _I, _I, _F, _F, _F, _F, _P]),
     "pn_cart_memory_build_f32": (_I, [C.POINTER(CartMemoryJob), _I, _P, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "pn_cart_memory_read_f32": (_I, [C.POINTER(CartMemoryJob), _I, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    "pn_roi_bev_gather_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "pn_roi_refine_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "pn_contract_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "pn_softmax_f32": (_I, [_P, _P, C.c_longlong, _I, _I, _P]),
     "pn_softmax_bwd_f32": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P]),
