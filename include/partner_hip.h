@@ -1703,6 +1703,68 @@ int pn_roi_refine_f32(const float *rois, const float *roi_scores, const int64_t 
                       int32_t *out_counts, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training of the CenterPoint second stage (det3d/models/roi_heads): proposal targets and the RoIHead's loss.  f32, no atomics, every
+ * sum in a fixed order (run to run bitwise), nothing read back, capturable in a hipGraph.  code_size cs = 7 | 9; rois (batch, R, cs)
+ * [x, y, z, w, l, h, rot, (vx, vy)], roi_labels (batch, R) int64, 1-based, 0 in padding slots (what pn_roi_bev_gather_f32 writes);
+ * gt (batch, N, cs + 1) [x, y, z, w, l, h, rot, (vx, vy,) class], zero rows at the end (two_stage.py:170-172).
+ *
+ * pn_roi_max_iou3d_f32 replaces det3d/models/roi_heads/target_assigner/proposal_target_layer.py:107-120, 210-244 and
+ * det3d/ops/iou3d_nms/iou3d_nms_utils.py:31-72 (boxes_iou3d_gpu).  Per sample the gt list is cut after the last row that is not all
+ * zeros (at least one row is kept).  IoU on the first 7 columns: to_pcdet (columns 3 / 4 swapped, rot' = -rot - pi / 2), the BEV
+ * overlap of the rotated footprints (the arithmetic of iou3d_nms_kernel.cu:104-215) times the height overlap clamped at 0, over
+ * max(vol_a + vol_b - overlap, 1e-6).  by_class != 0 (SAMPLE_ROI_BY_EACH_CLASS): only gts whose class equals the ROI's label compete,
+ * an ROI with no such gt gets (0, 0).  Ties go to the lowest gt index; a NaN IoU counts as 0, so gt_assignment always lies in [0, N).
+ *   out  max_overlaps (batch, R) f32, gt_assignment (batch, R) int32.
+ *
+ * pn_roi_sample_targets_f32 replaces proposal_target_layer.py:19-72, 94-208 (forward, sample_rois_for_rcnn, subsample_rois,
+ * sample_bg_inds) and roi_head_template.py:43-86 (assign_targets) in one launch (one block per sample; R <= 2048 and M <= 2048).
+ *   in   the above, roi_scores (batch, R), roi_features (batch, R, F) (F % 4 == 0, 16-byte aligned), max_overlaps / gt_assignment,
+ *        M = ROI_PER_IMAGE, FG_RATIO, REG_FG_THRESH, CLS_FG_THRESH, CLS_BG_THRESH, CLS_BG_THRESH_LO, HARD_BG_RATIO (the comparisons run
+ *        on their f32 values), score_type 0 = 'roi_iou' | 1 = 'cls', and the caller's uniform draws in [0, 1) (finite):
+ *        u_fg (batch, R), u_bg (batch, M).
+ *   Lists, each in ROI-slot order (nonzero()'s): fg = IoU >= min(REG_FG_THRESH, CLS_FG_THRESH); easy = not (IoU >= CLS_BG_THRESH_LO);
+ *   hard = CLS_BG_THRESH_LO <= IoU < REG_FG_THRESH.
+ *   THE DRAWS' CONTRACT (what np.random.permutation / np.random.rand / torch.randint stand for, proposal_target_layer.py:150, 161, 187-203):
+ *     foreground   the j-th fg ROI has key u_fg[b, j]; the picks are the first k = min(round_half_even(FG_RATIO * M), fg_num) entries of
+ *                  a stable ascending sort of the keys [0, fg_num), in sorted order: argsort(keys, stable)[:k].
+ *     background   with replacement; bg_needed = M - k.  hard_num = min(int(bg_needed * HARD_BG_RATIO), n_hard) (a double product) when
+ *                  both lists are non-empty; a single non-empty list takes all bg_needed picks.  Pick t < hard_num is
+ *                  hard[min(int(floorf(u_bg[b, t] * n_hard)), n_hard - 1)]; easy pick t is
+ *                  easy[min(int(floorf(u_bg[b, hard_num + t] * n_easy)), n_easy - 1)].  The product is an f32 product.
+ *     no background at all: all M picks are fg[min(int(floorf(u_bg[b, t] * fg_num)), fg_num - 1)].
+ *     Output row order: [fg picks, hard picks, easy picks].
+ *   out  each (batch, M, ...): sampled_inds int32; rois, roi_labels int64, roi_scores, gt_iou_of_rois, roi_features (row copies);
+ *        gt_of_rois_src (cs + 1) = the assigned gt row; gt_of_rois (cs + 1) = its encoding: columns 0:6 minus the ROI's, xyz rotated about
+ *        z by -roi_ry (rotate_points_along_z, box_torch_ops.py:124-142) with roi_ry = limit_period(roi[6], 0.5, 2 pi), column 6 =
+ *        (gt_rot - roi_ry) folded into [-pi / 2, pi / 2] (roi_head_template.py:74-82), cs == 9: the velocity difference, last column the
+ *        class; reg_valid_mask int64 = IoU > REG_FG_THRESH; rcnn_cls_labels f32: 'roi_iou' 1 above CLS_FG_THRESH, 0 below CLS_BG_THRESH,
+ *        (IoU - CLS_BG_THRESH) / (CLS_FG_THRESH - CLS_BG_THRESH) between (proposal_target_layer.py:54-62); 'cls' 1 / 0, -1 strictly between.
+ *
+ * pn_roi_loss_f32 replaces roi_head_template.py:88-151 (get_box_cls_layer_loss with CLS_LOSS 'BinaryCrossEntropy',
+ * get_box_reg_layer_loss with REG_LOSS 'L1', get_loss), forward and backward in one launch of one block.
+ *   in   rows (num_rows = batch * M, row_stride): the RoIHead's row buffer, rcnn_cls in column cls_col, rcnn_reg in columns
+ *        [reg_col, reg_col + cs); rcnn_cls_labels, gt_of_rois (num_rows, cs + 1), reg_valid_mask of the call above; code_weights: a HOST
+ *        array of cs floats.
+ *   out  loss[3] on the device = (rcnn_loss, rcnn_loss_cls, rcnn_loss_reg); d_rows (num_rows, row_stride) = d rcnn_loss / d rows, zeros
+ *        in every other column.  BCE on sigmoid(x) with torch's clamps (both logs at -100; backward (p - y) / max(p (1 - p), 1e-12) times
+ *        p (1 - p)), rows with label >= 0, over max(their count, 1).  L1: |reg - target| * code_weights on rows with reg_valid_mask > 0,
+ *        over max(their count, 1) (the reference's .item() is a device value here); gradient sign(.) with sign(0) = 0.
+ * Every entry: PN_ERR_INVALID without a launch on null pointers, cs not 7 or 9, batch / M / R / N / num_rows < 1, F % 4 != 0, feature
+ * rows that are not 16-byte aligned, columns that do not fit the row stride. */
+int pn_roi_max_iou3d_f32(const float *rois, const int64_t *roi_labels, const float *gt, int batch, int num_rois, int num_gt,
+                         int code_size, int by_class, float *max_overlaps, int32_t *gt_assignment, pn_stream_t stream);
+int pn_roi_sample_targets_f32(const float *rois, const int64_t *roi_labels, const float *roi_scores, const float *roi_features,
+                              const float *gt, const float *max_overlaps, const int32_t *gt_assignment, const float *u_fg,
+                              const float *u_bg, int batch, int num_rois, int num_gt, int code_size, int feature_cols,
+                              int roi_per_image, double fg_ratio, double reg_fg_thresh, double cls_fg_thresh, double cls_bg_thresh,
+                              double cls_bg_thresh_lo, double hard_bg_ratio, int score_type, int32_t *sampled_inds, float *out_rois,
+                              int64_t *out_labels, float *out_scores, float *out_ious, float *out_features, float *gt_of_rois_src,
+                              float *gt_of_rois, int64_t *reg_valid_mask, float *rcnn_cls_labels, pn_stream_t stream);
+int pn_roi_loss_f32(const float *rows, int num_rows, int row_stride, int cls_col, int reg_col, int code_size,
+                    const float *rcnn_cls_labels, const float *gt_of_rois, const int64_t *reg_valid_mask, const float *code_weights,
+                    float rcnn_cls_weight, float rcnn_reg_weight, float *loss, float *d_rows, pn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * next-4  global augmentation of one training sample, in place on the device: points (n, point_stride >= 3) [x, y, z, ...]
  * and boxes (m, box_cols = 7 | 9) [x, y, z, w, l, h, (vx, vy,) heading].  Order and arithmetic of
  * prep.random_flip_both / global_rotation / global_scaling_v2 / global_translate_

@@ -227,8 +227,14 @@ class PointPillars(SingleStageDetector):
     def forward_two_stage(self, example, return_loss=False, **kwargs):
         """the first stage of a TwoStageDetector (point_pillars.py:112-140, two_stage.py:155-166), inference: whatever ``extract_preds``
         accepts -> (the device list of ``bbox_head.predict(device_only=True)``, the NHWC neck output); nothing is read back"""
+        preds, x2 = self.two_stage_preds(example)
+        return first_stage_device_list(self, example, preds, return_loss, **kwargs), x2
+
+    def two_stage_preds(self, example):
+        """-> (the head's prediction dict, the NHWC neck output): what ``forward_two_stage`` decodes, and what ``TwoStageTrainStep`` takes the
+        first stage's loss from"""
         x1h, x2 = self._neck_maps(example)
-        return first_stage_device_list(self, example, self._heads(x1h, x2), return_loss, **kwargs), x2
+        return self._heads(x1h, x2), x2
 
     def _heads(self, x1_nhwc: torch.Tensor, x2_nhwc: torch.Tensor) -> Dict[str, object]:
         """point_pillars.py:91-96: the detection head on the RPN output, the segmentation head (when the config has one) on the
@@ -876,8 +882,14 @@ class VoxelNet(SingleStageDetector):
     def forward_two_stage(self, example, return_loss=False, **kwargs):
         """the first stage of a TwoStageDetector (voxelnet.py:133-168, two_stage.py:155-166), inference: whatever ``forward`` accepts ->
         (the device list of ``bbox_head.predict(device_only=True)``, the NHWC neck output); nothing is read back"""
+        preds, x = self.two_stage_preds(example)
+        return first_stage_device_list(self, example, preds, return_loss, **kwargs), x
+
+    def two_stage_preds(self, example):
+        """-> (the head's prediction dict, the NHWC neck output): what ``forward_two_stage`` decodes, and what ``TwoStageTrainStep`` takes the
+        first stage's loss from"""
         x = self._neck_map(example)
-        return first_stage_device_list(self, example, self.bbox_head(ops.as_nchw(x)), return_loss, **kwargs), x
+        return self.bbox_head(ops.as_nchw(x)), x
 
     def forward(self, example, return_loss=True, **kwargs):
         preds = self.bbox_head(ops.as_nchw(self._neck_map(example)))

@@ -170,11 +170,14 @@ class CenterHead(nn.Module):
     def loss(self, example, preds_dicts, **kwargs):
         """Forward value of the CenterPoint loss (center_head.py:248-288) on the HIP kernel.  Returns the
         reference's dict of per-task lists.  (No autograd graph: the backward kernels of the training step
-        are not built yet)"""
+        are not built yet)  ``device_only=True``: 'hm_loss' and 'loc_loss_elem' stay on the device instead of
+        the reference's ``.cpu()``, and nothing in the call synchronises with the host (``TwoStageTrainStep``)."""
         import ctypes as C
         from collections import defaultdict
         lib = hip.load()
         rets = defaultdict(list)
+        device_only = bool(kwargs.get("device_only", False))
+        cached = self.__dict__.setdefault("_code_weights_dev", {})      # (device, ndim) -> the code weights there: one upload
         for t, pd in enumerate(preds_dicts["det_preds"]):
             hm = pd["hm"]
             hip.require_device(hm)
@@ -192,7 +195,10 @@ class CenterHead(nn.Module):
             anno = example["anno_box"][t].to(dev).float().contiguous()
             ad = anno.shape[-1]
             sel = list(range(ndim)) if "vel" in pd else [0, 1, 2, 3, 4, 5, ad - 2, ad - 1]
-            cw = torch.tensor(list(self.code_weights)[:ndim], dtype=torch.float32, device=dev)
+            cw = cached.get((str(dev), ndim))
+            if cw is None:
+                host = torch.tensor(list(self.code_weights)[:ndim], dtype=torch.float32)
+                cw = cached[(str(dev), ndim)] = host.pin_memory().to(dev, non_blocking=True) if device_only else host.to(dev)
             out = torch.empty((4 + ndim,), dtype=torch.float32, device=dev)
             wsb = lib.pn_center_loss_workspace_bytes()
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
@@ -202,9 +208,9 @@ class CenterHead(nn.Module):
                      anno.data_ptr(), ad, (C.c_int * ndim)(*sel), ind.shape[1], ndim, cw.data_ptr(), float(self.weight),
                      out.data_ptr(), ws.data_ptr(), wsb, hip.stream())
             rets["det_loss"].append(out[0])
-            rets["hm_loss"].append(out[1].detach().cpu())
+            rets["hm_loss"].append(out[1].detach() if device_only else out[1].detach().cpu())
             rets["loc_loss"].append(out[2])
-            rets["loc_loss_elem"].append(out[4:].detach().cpu())
+            rets["loc_loss_elem"].append(out[4:].detach() if device_only else out[4:].detach().cpu())
             rets["num_positive"].append(out[3])
         return rets
 

@@ -481,3 +481,66 @@ def strat_channel_sum(dy: torch.Tensor, strata: int, out: torch.Tensor) -> torch
     cols = channel_sum(dy.view(1, b * h, 1, w * c))       # per (column, channel) over the rows, fixed order
     torch.sum(cols.view(strata, w // strata, c), dim=1, out=out.view(strata, c))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ second-stage training (roi_train.hip)
+ROI_SCORE_TYPES = {"roi_iou": 0, "cls": 1}
+
+
+def roi_max_iou3d(rois: torch.Tensor, roi_labels: torch.Tensor, gt: torch.Tensor, by_class: bool):
+    """`pn_roi_max_iou3d_f32`: rois (B, R, cs), roi_labels (B, R) int64, gt (B, N, cs + 1) -> max_overlaps (B, R) f32, gt_assignment (B, R) int32"""
+    hip.require_device(rois, roi_labels, gt)
+    b, r, cs = rois.shape
+    assert rois.dtype == torch.float32 and rois.is_contiguous() and gt.dtype == torch.float32 and gt.is_contiguous()
+    assert roi_labels.dtype == torch.int64 and roi_labels.is_contiguous() and tuple(roi_labels.shape) == (b, r)
+    assert gt.dim() == 3 and gt.shape[0] == b and gt.shape[2] == cs + 1, f"gt must be (B, N, {cs + 1}), got {tuple(gt.shape)}"
+    mo = torch.empty((b, r), dtype=torch.float32, device=rois.device)
+    ga = torch.empty((b, r), dtype=torch.int32, device=rois.device)
+    hip.call("pn_roi_max_iou3d_f32", rois.data_ptr(), roi_labels.data_ptr(), gt.data_ptr(), b, r, gt.shape[1], cs, int(bool(by_class)), mo.data_ptr(),
+             ga.data_ptr(), hip.stream())
+    return mo, ga
+
+
+def roi_sample_targets(rois, roi_labels, roi_scores, roi_features, gt, max_overlaps, gt_assignment, u_fg, u_bg, roi_per_image: int, fg_ratio: float,
+                       reg_fg_thresh: float, cls_fg_thresh: float, cls_bg_thresh: float, cls_bg_thresh_lo: float, hard_bg_ratio: float, score_type: str):
+    """`pn_roi_sample_targets_f32` -> the targets dict under the reference's keys (+ 'sampled_inds', 'gt_of_rois_src'), each (B, M, ...)"""
+    hip.require_device(rois, roi_labels, roi_scores, roi_features, gt, max_overlaps, gt_assignment, u_fg, u_bg)
+    b, r, cs = rois.shape
+    f, n, m, dev = roi_features.shape[2], gt.shape[1], int(roi_per_image), rois.device
+    for t, shape, dt in ((roi_scores, (b, r), torch.float32), (roi_features, (b, r, f), torch.float32), (max_overlaps, (b, r), torch.float32),
+                         (gt_assignment, (b, r), torch.int32), (u_fg, (b, r), torch.float32), (u_bg, (b, m), torch.float32),
+                         (roi_labels, (b, r), torch.int64), (gt, (b, n, cs + 1), torch.float32), (rois, (b, r, cs), torch.float32)):
+        assert tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous(), (tuple(t.shape), shape, t.dtype)
+    if score_type not in ROI_SCORE_TYPES:
+        raise NotImplementedError(f"CLS_SCORE_TYPE {score_type!r}: 'roi_iou' and 'cls' are built")
+    f32 = lambda *s: torch.empty((b, m) + s, dtype=torch.float32, device=dev)      # noqa: E731
+    out = dict(sampled_inds=torch.empty((b, m), dtype=torch.int32, device=dev), rois=f32(cs), roi_labels=torch.empty((b, m), dtype=torch.int64, device=dev),
+               roi_scores=f32(), gt_iou_of_rois=f32(), roi_features=f32(f), gt_of_rois_src=f32(cs + 1), gt_of_rois=f32(cs + 1),
+               reg_valid_mask=torch.empty((b, m), dtype=torch.int64, device=dev), rcnn_cls_labels=f32())
+    hip.call("pn_roi_sample_targets_f32", rois.data_ptr(), roi_labels.data_ptr(), roi_scores.data_ptr(), roi_features.data_ptr(), gt.data_ptr(),
+             max_overlaps.data_ptr(), gt_assignment.data_ptr(), u_fg.data_ptr(), u_bg.data_ptr(), b, r, n, cs, f, m, float(fg_ratio), float(reg_fg_thresh),
+             float(cls_fg_thresh), float(cls_bg_thresh), float(cls_bg_thresh_lo), float(hard_bg_ratio), ROI_SCORE_TYPES[score_type],
+             out["sampled_inds"].data_ptr(), out["rois"].data_ptr(), out["roi_labels"].data_ptr(), out["roi_scores"].data_ptr(),
+             out["gt_iou_of_rois"].data_ptr(), out["roi_features"].data_ptr(), out["gt_of_rois_src"].data_ptr(), out["gt_of_rois"].data_ptr(),
+             out["reg_valid_mask"].data_ptr(), out["rcnn_cls_labels"].data_ptr(), hip.stream())
+    return out
+
+
+def roi_loss(rows: torch.Tensor, cls_col: int, reg_col: int, code_size: int, rcnn_cls_labels, gt_of_rois, reg_valid_mask, code_weights,
+             rcnn_cls_weight: float, rcnn_reg_weight: float):
+    """`pn_roi_loss_f32` on the RoIHead's row buffer (rows, ld) -> (loss (3,) = (rcnn_loss, rcnn_loss_cls, rcnn_loss_reg) on the device,
+    d_rows (rows, ld))"""
+    hip.require_device(rows, rcnn_cls_labels, gt_of_rois, reg_valid_mask)
+    n, ld = rows.shape
+    assert rows.dtype == torch.float32 and rows.is_contiguous()
+    assert rcnn_cls_labels.dtype == torch.float32 and rcnn_cls_labels.is_contiguous() and rcnn_cls_labels.numel() == n
+    assert gt_of_rois.dtype == torch.float32 and gt_of_rois.is_contiguous() and gt_of_rois.numel() == n * (code_size + 1)
+    assert reg_valid_mask.dtype == torch.int64 and reg_valid_mask.is_contiguous() and reg_valid_mask.numel() == n
+    if len(code_weights) < code_size:
+        raise ValueError(f"LOSS_WEIGHTS.code_weights holds {len(code_weights)} values, code_size is {code_size}")
+    loss = torch.empty(3, dtype=torch.float32, device=rows.device)
+    d_rows = torch.empty_like(rows)
+    hip.call("pn_roi_loss_f32", rows.data_ptr(), n, ld, int(cls_col), int(reg_col), int(code_size), rcnn_cls_labels.data_ptr(), gt_of_rois.data_ptr(),
+             reg_valid_mask.data_ptr(), (C.c_float * code_size)(*[float(v) for v in code_weights[:code_size]]), float(rcnn_cls_weight),
+             float(rcnn_reg_weight), loss.data_ptr(), d_rows.data_ptr(), hip.stream())
+    return loss, d_rows

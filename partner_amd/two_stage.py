@@ -5,8 +5,9 @@ det3d/models/roi_heads/roi_head.py:16-106, roi_head_template.py:18-41, 153-183.
 
 The first stage leaves its detections on the device (``CenterHead.predict(device_only=True)``: fixed-capacity buffers and counts) and its
 neck output is NHWC already, so the second stage is `pn_roi_bev_gather_f32` -> the RoIHead's token GEMMs -> `pn_roi_refine_f32`: no
-per-sample Python loop, nothing read back, capturable in a hipGraph.  f32, eval mode; training of the second stage is not built (the
-reference's ProposalTargetLayer samples ROIs at random by 3-D IoU from a CUDA-only op: there is no CPU reference to pin it to).
+per-sample Python loop, nothing read back, capturable in a hipGraph.  f32, eval mode.  Training of the second stage on a frozen first stage
+has a surface of its own, ``train_two_stage.TwoStageTrainStep`` (proposal targets in roi_targets.py); ``forward(return_loss=True)``,
+``RoIHead.forward(training=True)`` and ``RoIHead.get_loss`` keep refusing.
 """
 from __future__ import annotations
 
@@ -248,6 +249,7 @@ class TwoStageDetector(nn.Module):
         super().__init__()
         self.single_det = builder.build_detector(first_stage_cfg, **kwargs)
         self.NMS_POST_MAXSIZE = int(NMS_POST_MAXSIZE)
+        self.freeze = bool(freeze)
         if freeze:      # the reference trains in two steps: the first stage stays as it was trained
             self.single_det.eval()
             self.single_det.requires_grad_(False)
@@ -265,6 +267,14 @@ class TwoStageDetector(nn.Module):
         self.num_point = int(num_point)
         self.test_cfg = kwargs.get("test_cfg")
         self._refuse_unbuilt(False)
+
+    def train(self, mode: bool = True):
+        """under ``freeze`` the first stage stays in eval form (the reference's ``SingleStageDetector.freeze`` turns its BatchNorms into
+        frozen ones, which ``train()`` does not touch)"""
+        super().train(mode)
+        if self.freeze:
+            self.single_det.eval()
+        return self
 
     def set_compute_dtype(self, dtype: str):
         if dtype != "f32":
