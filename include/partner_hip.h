@@ -1765,6 +1765,34 @@ int pn_roi_loss_f32(const float *rows, int num_rows, int row_stride, int cls_col
                     float rcnn_cls_weight, float rcnn_reg_weight, float *loss, float *d_rows, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Deformable convolution (DCN v1) forward of the CenterPoint DCN head (CenterHead(dcn_head=True), center_head.py:25-63, 111-163):
+ * 3x3, stride 1, pad 1, dilation 1, groups 1, `deformable_groups` offset groups, no bias, Cout = C, f32 NHWC, optional ReLU.
+ *
+ * pn_deform_conv3x3_f32 replaces det3d/ops/dcn/src/deform_conv_cuda_kernel.cu:191-243 (deformable_im2col_gpu_kernel) with :85-115
+ * (deformable_im2col_bilinear) and the column GEMM of det3d/ops/dcn/src/deform_conv_cuda.cpp:151-238, i.e. DeformConvFunction.forward
+ * (det3d/ops/dcn/deform_conv.py:16-60) -- as one implicit GEMM on the f32 MFMA: the sampled column matrix is never stored.
+ *   sample   output pixel (h, w), tap (i, j), group g: h_im = float(h - 1 + i) + off_h, w_im = float(w - 1 + j) + off_w with off_h = offset
+ *            channel g * 18 + 2 * (3 i + j) and off_w the next one; zero unless h_im > -1 && w_im > -1 && h_im < H && w_im < W, else bilinear
+ *            from floor(): every corner outside the map reads zero on its own, value = hh hw v1 + hh lw v2 + lh hw v3 + lh lw v4.  Group g
+ *            samples the input channels [g C / dg, (g + 1) C / dg).  out[p][n] = act(sum over (tap, c) of sample * weight[n][c][tap]).
+ *   jobs     ONE launch serves `jobs` convolutions of the same input map: job j reads the offset channels
+ *            [offset_channel_offset + 18 dg j, + 18 dg), the packed weight j (9 C C floats each, back to back) and writes the output channels
+ *            [out_channel_offset + C j, + C).  x: (batch, h, w) pixels of `x_pixel_stride` floats, the C input channels from
+ *            `x_channel_offset` (16-byte aligned base, stride and offset multiples of 4); offset / out likewise with their own strides.
+ *   No atomics, nothing allocated, no host synchronisation: capturable in a hipGraph; bitwise run to run.
+ *   The reference's zero padding of maps smaller than the kernel (deform_conv.py:242-254) is not needed: any h, w >= 1 runs.
+ * PN_ERR_INVALID without a launch: null pointers, C not 32 / 64 / 128, C / dg not a multiple of 4, act not none / ReLU, channel slices that
+ * do not fit their pixel stride, a misaligned x, batch / h / w / jobs < 1.
+ *
+ * pn_deform_conv3x3_pack_f32: weight (C, C, 3, 3) in torch layout (DeformConv.weight, deform_conv.py:226-228) -> [tap][n][c], the K-step
+ * slices the kernel copies to LDS; pn_deform_conv3x3_packed_weight_floats(C) = 9 C C. */
+size_t pn_deform_conv3x3_packed_weight_floats(int channels);
+int pn_deform_conv3x3_pack_f32(const float *weight, int channels, float *packed, pn_stream_t stream);
+int pn_deform_conv3x3_f32(const float *x, int x_pixel_stride, int x_channel_offset, const float *offset, int offset_pixel_stride,
+                          int offset_channel_offset, const float *packed_w, float *out, int out_pixel_stride, int out_channel_offset,
+                          int batch, int h, int w, int channels, int deformable_groups, int jobs, int act, pn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * next-4  global augmentation of one training sample, in place on the device: points (n, point_stride >= 3) [x, y, z, ...]
  * and boxes (m, box_cols = 7 | 9) [x, y, z, w, l, h, (vx, vy,) heading].  Order and arithmetic of
  * prep.random_flip_both / global_rotation / global_scaling_v2 / global_translate_

@@ -13,6 +13,7 @@ from __future__ import annotations
 import copy
 import ctypes as C
 import logging
+import math
 import os
 from typing import Dict, List
 
@@ -59,6 +60,54 @@ class SepHead(nn.Module):
                         nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
                         nn.init.constant_(m.bias, 0)
             setattr(self, head, fc)
+
+
+class DeformConv(nn.Module):
+    """parameters of the reference's DCN v1 layer (det3d/ops/dcn/deform_conv.py:185-237): ``weight`` only, uniform(+-1 / sqrt(Cin kh kw))"""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, padding=1, deformable_groups=1):
+        super().__init__()
+        if kernel_size != 3 or padding != 1:
+            raise NotImplementedError("DeformConv: only the 3x3 / stride 1 / pad 1 kernel is built (csrc/deform_conv.hip)")
+        self.in_channels, self.out_channels, self.deformable_groups = in_channels, out_channels, deformable_groups
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        stdv = 1.0 / math.sqrt(in_channels * kernel_size * kernel_size)
+        self.weight.data.uniform_(-stdv, stdv)
+
+
+class FeatureAdaption(nn.Module):
+    """parameters of the DCN feature adaption (center_head.py:25-63): a 1x1 convolution predicts the offsets (its weight starts at zero) of
+    a deformable 3x3 convolution, followed by ReLU"""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, deformable_groups=4):
+        super().__init__()
+        self.conv_offset = nn.Conv2d(in_channels, deformable_groups * kernel_size * kernel_size * 2, 1, bias=True)
+        self.conv_adaption = DeformConv(in_channels, out_channels, kernel_size=kernel_size, padding=(kernel_size - 1) // 2,
+                                        deformable_groups=deformable_groups)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv_offset.weight.data.zero_()
+
+
+class DCNSepHead(nn.Module):
+    """per-task heads of CenterHead(dcn_head=True) (center_head.py:111-163): separate deformable adaptions for classification and
+    regression, the heat-map head (conv + BatchNorm2d(64) + ReLU + conv) on the first, a SepHead of the regression targets on the second"""
+
+    def __init__(self, in_channels, num_cls, heads, head_conv=64, final_kernel=1, bn=False, init_bias=-2.19, **kwargs):
+        super().__init__()
+        self.feature_adapt_cls = FeatureAdaption(in_channels, in_channels, kernel_size=3, deformable_groups=4)
+        self.feature_adapt_reg = FeatureAdaption(in_channels, in_channels, kernel_size=3, deformable_groups=4)
+        self.cls_head = Sequential(nn.Conv2d(in_channels, head_conv, kernel_size=3, padding=1, bias=True),
+                                   nn.BatchNorm2d(64),      # hard-coded 64, as in the reference (:143)
+                                   nn.ReLU(inplace=True),
+                                   nn.Conv2d(head_conv, num_cls, kernel_size=3, stride=1, padding=1, bias=True))
+        self.cls_head[-1].bias.data.fill_(init_bias)
+        self.task_head = SepHead(in_channels, heads, head_conv=head_conv, bn=bn, final_kernel=final_kernel)
+
+
+def _refuse_dcn(dcn_head, what: str) -> None:
+    if dcn_head:
+        raise NotImplementedError(f"{what}: dcn_head=True is built for the plain CenterHead only (DCNSepHead, center_head.py:111-163); "
+                                  f"{what} has no deformable-convolution form of its merged branches")
 
 
 def _dense_weight(conv: nn.Conv2d) -> torch.Tensor:
@@ -129,19 +178,60 @@ class CenterHead(nn.Module):
         self.use_direction_classifier = False
         self.logger = logger or logging.getLogger("CenterHead")
         self.logger.info(f"num_classes: {num_classes}")
-        if dcn_head:
-            raise NotImplementedError("dcn_head=True (deformable convolution head) is outside the hot path (SURVEY.md 2.1)")
+        self.dcn_head = bool(dcn_head)
         self.shared_conv = nn.Sequential(nn.Conv2d(in_channels, share_conv_channel, kernel_size=3, padding=1, bias=True),
                                          nn.ReLU(inplace=True))
         self.tasks = nn.ModuleList()
         for ncls in num_classes:
             heads = copy.deepcopy(common_heads)
+            if dcn_head:      # center_head.py:227-230
+                self.tasks.append(DCNSepHead(share_conv_channel, ncls, heads, bn=True, init_bias=init_bias, final_kernel=3))
+                continue
             heads.update(dict(hm=(ncls, num_hm_conv)))
             self.tasks.append(SepHead(share_conv_channel, heads, bn=True, init_bias=init_bias, final_kernel=3))
         self._plan = PlanCache()
         self.logger.info("Finish CenterHead Initialization")
 
+    def _build_dcn_plan(self):
+        """dcn_head=True: the shared convolution, ONE 1x1 convolution for every adaption's offsets (cls and reg of each task, side by side),
+        ONE deformable launch of 2T jobs + ReLU, then per task the heat-map head (BatchNorm folded) on the cls slice and the regression
+        chains on the reg slice"""
+        adapts = [fa for task in self.tasks for fa in (task.feature_adapt_cls, task.feature_adapt_reg)]
+        dg = adapts[0].conv_adaption.deformable_groups
+        offset = ops.ConvLayer(torch.cat([fa.conv_offset.weight for fa in adapts], 0), stride=1, pad=0,
+                               shift=torch.cat([fa.conv_offset.bias for fa in adapts], 0), act=ops.ACT_NONE)
+        deform = ops.DeformConvLayer([fa.conv_adaption.weight for fa in adapts], dg=dg, act=ops.ACT_RELU)
+        plan = dict(shared=_conv_bias(self.shared_conv[0], ops.ACT_RELU), offset=offset, deform=deform, tasks=[])
+        for task in self.tasks:
+            c0, bn, c1 = task.cls_head[0], task.cls_head[1], task.cls_head[3]
+            scale, shift = ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, c0.bias)
+            heads = dict(hm=[ops.ConvLayer(c0.weight, stride=1, pad=c0.padding[0], scale=scale, shift=shift, act=ops.ACT_RELU),
+                             _conv_bias(c1, ops.ACT_NONE)])
+            for name in task.task_head.heads:
+                convs = [m for m in getattr(task.task_head, name)._modules.values() if isinstance(m, nn.Conv2d)]
+                heads[name] = [_conv_bias(c, ops.ACT_RELU if k < len(convs) - 1 else ops.ACT_NONE) for k, c in enumerate(convs)]
+            plan["tasks"].append(heads)
+        return plan
+
+    def _forward_dcn(self, plan, x):
+        xs = plan["shared"](ops.to_nhwc(x))
+        feats = plan["deform"](xs, plan["offset"](xs))      # (B, H, W, 2T C): task t's cls features at 2t C, its reg features at (2t + 1) C
+        c = plan["deform"].c
+        rets: List[Dict[str, torch.Tensor]] = []
+        for t, heads in enumerate(plan["tasks"]):
+            d = {}
+            for name, layers in heads.items():
+                y = layers[0](feats, in_channel_offset=(2 * t if name == "hm" else 2 * t + 1) * c)
+                for layer in layers[1:]:
+                    y = layer(y)
+                d[name] = ops.as_nchw(y)
+            d["hm"] = d.pop("hm")      # the reference's key order: the regression heads, then 'hm' (center_head.py:160-161)
+            rets.append(d)
+        return {"det_preds": rets}
+
     def _build_plan(self):
+        if self.dcn_head:
+            return self._build_dcn_plan()
         plan = dict(shared=_conv_bias(self.shared_conv[0], ops.ACT_RELU), tasks=[])
         for task in self.tasks:
             heads = {}
@@ -155,6 +245,8 @@ class CenterHead(nn.Module):
         hip.require_device(x)
         eval_only(self, type(self).__name__)
         plan = self._plan.get(self, self._build_plan)
+        if self.dcn_head:
+            return self._forward_dcn(plan, x)
         xs = plan["shared"](ops.to_nhwc(x))
         rets: List[Dict[str, torch.Tensor]] = []
         for heads in plan["tasks"]:
@@ -457,6 +549,7 @@ class CenterHeadSingle(CenterHead):
     def __init__(self, in_channels=[128, ], tasks=[], dataset="nuscenes", weight=0.25, code_weights=[], common_heads=dict(),
                  logger=None, init_bias=-2.19, share_conv_channel=64, num_hm_conv=2, dcn_head=False, voxel_shape="cuboid",
                  act="ReLU"):
+        _refuse_dcn(dcn_head, type(self).__name__)
         super().__init__(in_channels, tasks, dataset, weight, code_weights, common_heads, logger, init_bias,
                          share_conv_channel, num_hm_conv, dcn_head, voxel_shape)
         if act != "ReLU":
@@ -879,6 +972,7 @@ class CenterHeadSinglePos(CenterHeadSingle):
     def __init__(self, in_channels=[128, ], tasks=[], dataset="nuscenes", weight=0.25, code_weights=[], common_heads=dict(),
                  logger=None, init_bias=-2.19, share_conv_channel=64, num_hm_conv=2, dcn_head=False, voxel_shape="cuboid",
                  voxel_generator=None, out_size_factor=4):
+        _refuse_dcn(dcn_head, type(self).__name__)
         super().__init__(in_channels, tasks, dataset, weight, code_weights, common_heads, logger, init_bias,
                          share_conv_channel, num_hm_conv, dcn_head, voxel_shape)
         head_conv = 64

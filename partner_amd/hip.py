@@ -324,6 +324,9 @@ SIGNATURES = {
     "pn_roi_max_iou3d_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "pn_roi_sample_targets_f32": (_I, [_P] * 9 + [_I] * 6 + [C.c_double] * 6 + [_I] + [_P] * 10 + [_P]),
     "pn_roi_loss_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P]),
+    "pn_deform_conv3x3_packed_weight_floats": (_SZ, [_I]),
+    "pn_deform_conv3x3_pack_f32": (_I, [_P, _I, _P, _P]),
+    "pn_deform_conv3x3_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "pn_contract_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "pn_softmax_f32": (_I, [_P, _P, C.c_longlong, _I, _I, _P]),
     "pn_softmax_bwd_f32": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P]),

@@ -15,6 +15,7 @@ from .ops_common import *  # noqa: F401,F403
 from .ops_common import _f32, _workspace  # noqa: F401
 from .ops_conv import *  # noqa: F401,F403
 from .ops_conv import _chain_orientation  # noqa: F401
+from .ops_deform import *  # noqa: F401,F403
 from .ops_index import *  # noqa: F401,F403
 from .ops_token import *  # noqa: F401,F403
 from .ops_train import *  # noqa: F401,F403

@@ -101,6 +101,9 @@ class E2ESWVoteHead(nn.Module):
                  logger=None, init_bias=-2.19, share_conv_channel=64, num_hm_conv=2, dcn_head=False, voxel_shape="cuboid",
                  voxel_generator=None, out_size_factor=4, npixels=0, SET_CRIT_CONFIG=dict(), MATCHER_CONFIG=dict(),
                  USE_FOCAL_LOSS=True, GT_PROCESSOR_CONFIG=dict(), CODER_CONFIG=dict(), HEAD_CONFIG=dict()):
+        if dcn_head:
+            raise NotImplementedError("E2ESWVoteHead: dcn_head=True is built for the plain CenterHead only (DCNSepHead, center_head.py:111-163); "
+                                      "the geometry-aware head has no deformable-convolution branches")
         super().__init__()
         head_conv = 64
         self.dataset, self.voxel_shape, self.period = dataset, voxel_shape, 2 * np.pi

@@ -69,8 +69,16 @@ class _ConvBranch(_NormBranch):
         self.last = _Conv(ps, prefix + "3.weight", prefix + "3.bias", 1, 1) if groups == 1 else _GroupedConv(ps, prefix + "3.weight", prefix + "3.bias", groups)
 
 
+def refuse_dcn_training(head: nn.Module, what: str) -> None:
+    """CenterHead(dcn_head=True) runs inference only: the deformable convolution has a forward kernel (csrc/deform_conv.hip) and no backward"""
+    if getattr(head, "dcn_head", False):
+        raise NotImplementedError(f"{what}: dcn_head=True is not trained -- the backward of the deformable convolution (col2im into the input "
+                                  "gradient and the offset gradient, deform_conv_cuda_kernel.cu:279-465) is not built")
+
+
 class CenterHeadTrain:
     def __init__(self, ps, head: nn.Module, dev, prefix="bbox_head."):
+        refuse_dcn_training(head, "CenterHeadTrain")
         self.ps, hp = ps, prefix
         self.plain = type(head).__name__ == "CenterHead"
         self.code_weights, self.loss_weight = list(head.code_weights), float(head.weight)
