@@ -715,7 +715,10 @@ int pn_setblock_keypoints(const float *chan_mean, const float *xn, const float *
                           int w, int c, int k, int shift, int col_major, int32_t *top_idx, float *kp,
                           float *kpos, pn_stream_t stream);
 /* SectorAttention core: key points attend to their column (set_transformer.py:307-354).
- * q_raw: proj_q(kp) (B, k*W, C) read through the reference's raw (B,C,k,W) view; kv: (tokens, 2C) */
+ * q_raw: proj_q(kp) (B, k*W, C) read through the reference's raw (B,C,k,W) view; kv: (tokens, 2C), 16-byte aligned like out.
+ * heads <= 4, head width a multiple of 4 and <= 64, k <= 8; LDS: 5 k C floats of queries and row-chunk partials plus
+ * heads k h floats of logits ROUNDED UP to a multiple of 4 (the partials behind them are float4 stores), 64 KB at most:
+ * h <= 192 for k = 8, C = 256, heads = 4. */
 int pn_setblock_sector_kp_attn(const float *q_raw, const float *kv, const float *xpos,
                                const float *kpos, const float *pos_mlp, int batch, int h, int w, int c,
                                int heads, int k, int shift, int col_major, float scale, float *out,

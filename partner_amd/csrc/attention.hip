@@ -201,7 +201,7 @@ __global__ __launch_bounds__(1024) void sector_kp_attn_kernel(const float* __res
   const int b = blockIdx.x / W, wr = blockIdx.x % W, wp = (wr + shift) % W;
   float* qs = lds;                         // [heads][K][hd]
   float* ps = qs + heads * K * hd;         // [heads][K][H]
-  float* part = ps + heads * K * H;        // [SKP_CH][heads][K][hd]
+  float* part = ps + ((heads * K * H + 3) & ~3);      // [SKP_CH][heads][K][hd], written as f32x4: starts on a multiple of 4 floats
   const float* qb = qraw + (size_t)b * K * W * C;
   for (int i = tid; i < heads * K * hd; i += 1024) {
     const int hh = i / (K * hd), r = i - hh * (K * hd), k = r / hd, d = r - k * hd;
@@ -524,7 +524,8 @@ int pn_setblock_sector_kp_attn(const float* q_raw, const float* kv, const float*
   PN_REQUIRE(q_raw && kv && xpos && kpos && pos_mlp && out, "sector_kp_attn: null pointer");
   PN_REQUIRE(heads >= 1 && heads <= 4 && c % heads == 0 && (c / heads) % 4 == 0 && c / heads <= 64 && k <= 8, "sector_kp_attn: bad sizes (head width <= 64)");
   PN_REQUIRE(((uintptr_t)kv & 15) == 0 && ((uintptr_t)out & 15) == 0 && c % 4 == 0, "sector_kp_attn: 16-byte aligned buffers");
-  const size_t smem = ((size_t)heads * k * (c / heads) * (1 + SKP_CH) + (size_t)heads * k * h) * sizeof(float);
+  // q | logits (rounded up to whole float4: the row-chunk partials behind them are float4 stores) | SKP_CH partials
+  const size_t smem = ((size_t)heads * k * (c / heads) * (1 + SKP_CH) + (((size_t)heads * k * h + 3) & ~(size_t)3)) * sizeof(float);
   PN_REQUIRE(smem <= 64 * 1024, "sector_kp_attn: column too long for LDS");
   PosMlp pm{pos_mlp, heads};
   if (k <= 4)
