@@ -1795,6 +1795,43 @@ int pn_deform_conv3x3_f32(const float *x, int x_pixel_stride, int x_channel_offs
                           int offset_channel_offset, const float *packed_w, float *out, int out_pixel_stride, int out_channel_offset,
                           int batch, int h, int w, int channels, int deformable_groups, int jobs, int act, pn_stream_t stream);
 
+/* Backward of pn_deform_conv3x3_f32 (csrc/deform_conv_bwd.hip), same scope, same maps and job layout.  dz = dout, or dout * (out > 0)
+ * when act = ReLU (`out` = the saved forward output; it may be NULL when act = none).  dout / out: job j's channels [offset + C j, + C) of
+ * their maps (16-byte aligned bases, strides and offsets multiples of 4).
+ *
+ * pn_deform_conv3x3_bwd_data_f32 replaces deformable_col2im_gpu_kernel (det3d/ops/dcn/src/deform_conv_cuda_kernel.cu:279-335, with
+ * get_gradient_weight :117-143), deformable_col2im_coord_gpu_kernel (:371-465, with get_coordinate_weight :146-188) and their column GEMM
+ * (deform_conv_cuda.cpp:240-353, deform_conv_backward_input_cuda) behind DeformConvFunction.backward (det3d/ops/dcn/deform_conv.py:62-90):
+ *   d_offset  job j's channels [doffset_channel_offset + 18 dg j, + 18 dg) in the offsets' own order (group, tap, (dh, dw)):
+ *             sum over the group's channels of dS * dS/d(h or w), the derivative with floor() held constant, zero when the sample position
+ *             is off the map (h_im <= -1 || w_im <= -1 || h_im >= H || w_im >= W).  One writer per element, a fixed summation order.
+ *   d_x       the channels [dx_channel_offset, + C) of the d_x map, the sum over ALL jobs of the bilinear scatter of dS; written, or added
+ *             when `accumulate`.  NULL: only d_offset is computed.  The scatter is an order-independent 64-bit fixed-point sum (integer
+ *             atomicAdd, a per-launch power-of-two scale from max |dz| and the weights): bitwise reproducible, no float atomics; scaling
+ *             dout by a power of two scales the result exactly; a non-finite dz makes every d_x element NaN; dz = 0 gives exact zeros.
+ *   packed_wt the weights as pn_deform_conv3x3_pack_bwd_f32 lays them out: [job][tap][c][n], 9 C C floats per job.
+ * pn_deform_conv3x3_bwd_weight_f32 replaces deform_conv_backward_parameters_cuda (deform_conv_cuda.cpp:356-488; deform_conv.py:92-104):
+ *   d_weights a HOST array of `jobs` device pointers, each a (C, C, 3, 3) tensor in torch layout: written, or added to when `wacc`.  The
+ *             pixel range is cut into at most 16 slices whose partial sums are added in a fixed order.
+ * Both take the same caller-provided workspace of pn_deform_conv3x3_bwd_workspace_bytes (0 for a shape that is refused) and use disjoint
+ * parts of it, so they may run on two streams at once.  Nothing is allocated, nothing synchronises with the host, every launch is capturable.
+ * PN_ERR_INVALID without a launch: null pointers, C not 32 / 64 / 128, C / dg not a multiple of 4, act not none / ReLU, channel slices that
+ * do not fit their pixel stride, misaligned x / dout / out, batch / h / w / jobs < 1, maps past 32-bit pixel indices, a workspace that is
+ * too small or not 16-byte aligned. */
+size_t pn_deform_conv3x3_bwd_workspace_bytes(int batch, int h, int w, int channels, int jobs);
+int pn_deform_conv3x3_pack_bwd_f32(const float *weight, int channels, float *packed_t, pn_stream_t stream);
+int pn_deform_conv3x3_bwd_data_f32(const float *x, int x_pixel_stride, int x_channel_offset, const float *offset, int offset_pixel_stride,
+                                   int offset_channel_offset, const float *packed_wt, const float *out, int out_pixel_stride,
+                                   int out_channel_offset, const float *dout, int dout_pixel_stride, int dout_channel_offset, float *d_x,
+                                   int dx_pixel_stride, int dx_channel_offset, int accumulate, float *d_offset, int doffset_pixel_stride,
+                                   int doffset_channel_offset, int batch, int h, int w, int channels, int deformable_groups, int jobs,
+                                   int act, void *workspace, size_t workspace_bytes, pn_stream_t stream);
+int pn_deform_conv3x3_bwd_weight_f32(const float *x, int x_pixel_stride, int x_channel_offset, const float *offset, int offset_pixel_stride,
+                                     int offset_channel_offset, const float *out, int out_pixel_stride, int out_channel_offset,
+                                     const float *dout, int dout_pixel_stride, int dout_channel_offset, float *const *d_weights, int wacc,
+                                     int batch, int h, int w, int channels, int deformable_groups, int jobs, int act, void *workspace,
+                                     size_t workspace_bytes, pn_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * next-4  global augmentation of one training sample, in place on the device: points (n, point_stride >= 3) [x, y, z, ...]
  * and boxes (m, box_cols = 7 | 9) [x, y, z, w, l, h, (vx, vy,) heading].  Order and arithmetic of

@@ -327,6 +327,10 @@ SIGNATURES = {
     "pn_deform_conv3x3_packed_weight_floats": (_SZ, [_I]),
     "pn_deform_conv3x3_pack_f32": (_I, [_P, _I, _P, _P]),
     "pn_deform_conv3x3_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "pn_deform_conv3x3_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "pn_deform_conv3x3_pack_bwd_f32": (_I, [_P, _I, _P, _P]),
+    "pn_deform_conv3x3_bwd_data_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _I, _I] + [_I] * 7 + [_P, _SZ, _P]),
+    "pn_deform_conv3x3_bwd_weight_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I] + [_I] * 7 + [_P, _SZ, _P]),
     "pn_contract_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "pn_softmax_f32": (_I, [_P, _P, C.c_longlong, _I, _I, _P]),
     "pn_softmax_bwd_f32": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P]),

@@ -32,7 +32,7 @@ from . import hip, ops
 from .routes import R
 from .heads import CenterHeadSingle
 from .readers import DynamicPFNet
-from .train_head import CenterHeadTrain, refuse_dcn_training
+from .train_head import CenterHeadTrain
 from .train_layers import _ConvBNReLU, _PillarConv      # (_PillarConv: tests import it from here)
 
 
@@ -316,7 +316,6 @@ class PolarPillarTrainStep(OptimizerForwards):
             raise NotImplementedError("training step: the reader must be a DynamicPFNet")
         if not (isinstance(head, CenterHeadSingle) or type(head).__name__ == "CenterHead"):
             raise NotImplementedError("training step: the head must be CenterHead, CenterHeadSingle or CenterHeadSinglePos")
-        refuse_dcn_training(head, "training step")
         reader._check_supported()
         dev = next(model.parameters()).device
         hip.require_device(next(model.parameters()))

@@ -163,18 +163,21 @@ class _GroupedConv:
 
 
 class _ConvBNReLU:
-    """Conv2d / ConvTranspose2d (no bias) + BatchNorm2d (batch statistics) + ReLU  (rpn.py:124-142, 80-110)"""
+    """Conv2d / ConvTranspose2d + BatchNorm2d (batch statistics) + ReLU  (rpn.py:124-142, 80-110: no bias; the heat-map head of DCNSepHead,
+    center_head.py:141-146: a convolution WITH a bias -- the batch mean takes it out again, so its gradient, the channel sum of the
+    BatchNorm backward's output, is zero up to rounding)"""
 
     def __init__(self, ps, prefix: str, conv_idx: int, bn: nn.BatchNorm2d, conv: nn.Module):
         transposed = isinstance(conv, nn.ConvTranspose2d)
         pad = 1 if conv.kernel_size[0] == 3 else 0  # nn.ZeroPad2d(1) + Conv2d(3, padding=0) == padding 1
-        self.conv = _Conv(ps, f"{prefix}{conv_idx}.weight", None, conv.stride[0], pad, NONE, transposed)
+        bias = f"{prefix}{conv_idx}.bias" if getattr(conv, "bias", None) is not None else None
+        self.conv = _Conv(ps, f"{prefix}{conv_idx}.weight", bias, conv.stride[0], pad, NONE, transposed)
         self.gname, self.bname = f"{prefix}{conv_idx + 1}.weight", f"{prefix}{conv_idx + 1}.bias"
         self.ps, self.bn = ps, bn
         self.y = self.stat = None
 
-    def fwd(self, x, out=None, out_co=0):
-        self.y = self.conv.fwd(x)
+    def fwd(self, x, out=None, out_co=0, in_co=0):
+        self.y = self.conv.fwd(x, in_co=in_co)
         res, self.stat = ops.batchnorm_train(self.y, self.ps.p[self.gname], self.ps.p[self.bname], self.bn.eps, self.bn.momentum,
                                              self.bn.running_mean, self.bn.running_var, act=RELU, out=out, out_channel_offset=out_co)
         return res
@@ -189,13 +192,13 @@ class _ConvBNReLU:
     def restore(self, saved):
         self.conv.x, self.conv.in_co, self.y, self.stat = saved
 
-    def bwd(self, dout, dout_co=0, need_dx=True, dx=None, accumulate=False, wacc=False):
+    def bwd(self, dout, dout_co=0, need_dx=True, dx=None, accumulate=False, wacc=False, dx_co=0):
         c = self.y.shape[3]
         inplace = dout.shape[3] == c and dout_co == 0
         dy = dout if inplace else torch.empty_like(self.y)
         ops.batchnorm_bwd(self.y, dout, self.ps.p[self.gname], self.ps.p[self.bname], self.stat, act=RELU, dx=dy,
                           dgamma=self.ps.g[self.gname], dbeta=self.ps.g[self.bname], dout_channel_offset=dout_co, accumulate=wacc)
-        return self.conv.bwd(dy, need_dx=need_dx, dx=dx, accumulate=accumulate, wacc=wacc)
+        return self.conv.bwd(dy, need_dx=need_dx, dx=dx, dx_co=dx_co, accumulate=accumulate, wacc=wacc)
 
 
 class _ConvReLU:
@@ -205,13 +208,13 @@ class _ConvReLU:
         self.conv = _Conv(ps, wname, bname, 1, pad, act=RELU)
         self.z = None
 
-    def fwd(self, x):
-        self.z = self.conv.fwd(x)   # ReLU fused into the epilogue; its output is also the backward mask
+    def fwd(self, x, in_co=0):
+        self.z = self.conv.fwd(x, in_co=in_co)   # ReLU fused into the epilogue; its output is also the backward mask
         return self.z
 
-    def bwd(self, dout, dx=None, accumulate=False):
+    def bwd(self, dout, dx=None, accumulate=False, dx_co=0):
         dy = ops.relu_bwd(self.z, dout, dx=dout)
-        return self.conv.bwd(dy, dx=dx, accumulate=accumulate)
+        return self.conv.bwd(dy, dx=dx, dx_co=dx_co, accumulate=accumulate)
 
 
 class _ConvGNReLU:
