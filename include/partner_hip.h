@@ -1119,6 +1119,40 @@ int pn_sparse_to_dense_nhwc(const float *feats, const uint32_t *keys, int capaci
  * element is stored once in the map's own order, no zero fill and no scatter (c a multiple of 4).  scn.py:176-179. */
 int pn_sparse_to_dense_index_nhwc(const float *feats, const void *index_buf, const int32_t *dims, int c, float *out, pn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Voxel-wise segmentation (csrc/voxel_seg.hip): DeconvConvHead with height D > 1 (seg_heads/seg_head.py:195-264) evaluated at a list of
+ * cells instead of as a dense (17 D -> NC D)-channel 3x3 convolution over the whole map.  f32, inference.
+ *   pn_deconv_overlap_f32      UpsampleShelhamer = ConvTranspose2d(Cin -> D, kernel 2S, stride S, padding S/2, no bias) after ONE GEMM:
+ *                              cols (B h w, 2S 2S D) = x (B h w, Cin) x W, column (ky 2S + kx) D + c  ->  out (B, h S, w S, D) NHWC, every
+ *                              element the sum of its at most 2 x 2 column entries in (iy, ix) ascending order.  S even.
+ *   pn_voxel_seg_logits_f32    out[q][0 .. NCpad) = the head's logits of cell queries[q] (a key ((b D + z) H + y) W + x of `dims` = [B, D, H, W];
+ *                              any cells, active or not, in any order, repeated or not) for q < min(*n_dev, n_capacity); later rows are not
+ *                              written, a key outside the grid gives a row of zeros.  index_buf / feats: the level's index
+ *                              (pn_sparse_index_*) and its (rows, 16) conv1 features in key order; u: (B, H, W, D) NHWC.
+ *                              NCpad = pn_voxel_seg_class_pad(NC) (4, 8, 16 or 32; 0: not built); packed_w:
+ *                              [z][D slabs z' | ceil(D / 16) slabs of 16 channels of u][tap][16][NCpad] floats
+ *                              (pn_voxel_seg_packed_weight_floats; rows past D and classes past NC zero), packed_bias [z][NCpad].
+ *                              A row's value does not depend on the other rows of the list.  D <= 256.
+ *   pn_voxel_seg_point_labels  labels[i] = 1 + argmax (lowest class among equals) of the row of point i's cell, rows = the logits of the
+ *                              level's ACTIVE set in key order; grid_ind (n, 3) int64 [z, y, x], offsets (B + 1) int32 the samples' first
+ *                              rows.  A point outside the grid or of no sample gets 0.  A point whose cell is not active gets 0 and,
+ *                              with the (nullable) miss list, an entry (cell key, point row) at miss_keys / miss_rows[0 .. *miss_count)
+ *                              (n entries each, in no fixed order; the count is zeroed first): the caller runs
+ *                              pn_voxel_seg_logits_f32 over miss_keys and pn_voxel_seg_scatter_labels(rows, NC, miss_rows, n, miss_count, n, labels)
+ *                              (labels[dest[j]] = the label of row j).  Nothing is read back.
+ */
+int pn_voxel_seg_class_pad(int num_classes);
+size_t pn_voxel_seg_packed_weight_floats(int depth, int num_classes);
+int pn_deconv_overlap_f32(const float *cols, int batch, int h, int w, int up_scale, int channels, float *out, pn_stream_t stream);
+int pn_voxel_seg_logits_f32(const uint32_t *queries, int n_capacity, const int32_t *n_dev, const int32_t *dims, const void *index_buf,
+                            const float *feats, const float *u, const float *packed_w, const float *packed_bias, int num_classes,
+                            float *out, pn_stream_t stream);
+int pn_voxel_seg_point_labels(const float *rows, int num_classes, const void *index_buf, const int32_t *dims, const int64_t *grid_ind,
+                              const int32_t *offsets, int n_points, int64_t *labels, uint32_t *miss_keys, int32_t *miss_rows,
+                              int32_t *miss_count, pn_stream_t stream);
+int pn_voxel_seg_scatter_labels(const float *rows, int num_classes, const int32_t *dest, int capacity, const int32_t *n_dev, int n_labels,
+                                int64_t *labels, pn_stream_t stream);
+
 /* Backward side of the sparse convolutions (scn.py:97-192 under autograd; spconv's own backward in the reference).
  *   pn_sparse_neighbors_transpose  inv[in row][tap] = the output row that reads it through that tap, or -1 (at most one
  *                                  exists): the data gradient is then pn_sparse_conv_f32 over `inv` with the (Cin, Cout)

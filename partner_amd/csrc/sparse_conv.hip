@@ -11,29 +11,14 @@
 //   neighbour table  nbr[out site][tap] = input index or -1    (one table per indice_key, reused by every conv of it)
 // The convolution itself is pn_sparse_conv_f32 (conv_mfma.hip, gather mode).
 #include "pn_common.h"
+#include "sparse_index.h"
 #include <algorithm>
 
 namespace {
 
-constexpr int kT = 256, kItems = 8, kTile = kT * kItems;  // words per scan tile
+using namespace pn_sparse;      // Dims, make_key / split_key / lookup, IndexBuf (sparse_index.h)
 
-struct Dims { int B, D, H, W; };
 struct Geo { int k[3], s[3], p[3]; };
-
-__device__ __forceinline__ uint32_t make_key(const Dims& d, int b, int z, int y, int x) { return (uint32_t)(((b * d.D + z) * d.H + y) * d.W + x); }
-
-__device__ __forceinline__ void split_key(const Dims& d, uint32_t key, int& b, int& z, int& y, int& x) {
-  x = key % d.W; key /= d.W;
-  y = key % d.H; key /= d.H;
-  z = key % d.D; b = key / d.D;
-}
-
-__device__ __forceinline__ int lookup(const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ word_rank, uint32_t key) {
-  const uint32_t w = key >> 5, bit = key & 31, bits = bitmap[w];
-  if (!((bits >> bit) & 1u)) return -1;
-  return (int)(word_rank[w] + __popc(bits & ((1u << bit) - 1u)));
-}
-
 
 __global__ void mark_coords_kernel(const int32_t* __restrict__ coords, int n_cap, const int32_t* __restrict__ n_dev, Dims d, uint32_t* __restrict__ bitmap) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -237,19 +222,6 @@ __global__ void to_dense_lookup_kernel(const float* __restrict__ feats, const ui
   }
 }
 
-struct IndexBuf {
-  uint32_t* bitmap; uint32_t* word_rank; uint32_t* tiles; size_t nwords; int ntiles; size_t bytes;
-  IndexBuf(void* base, uint64_t cells) {
-    nwords = (size_t)((cells + 31) / 32);
-    ntiles = (int)((nwords + kTile - 1) / kTile);
-    char* p = static_cast<char*>(base);
-    bitmap = reinterpret_cast<uint32_t*>(p); p += (nwords * 4 + 255) / 256 * 256;
-    word_rank = reinterpret_cast<uint32_t*>(p); p += (nwords * 4 + 255) / 256 * 256;
-    tiles = reinterpret_cast<uint32_t*>(p); p += ((size_t)ntiles * 4 + 255) / 256 * 256;
-    bytes = (size_t)(p - static_cast<char*>(base));
-  }
-};
-
 int scan_and_emit(const IndexBuf& ib, uint32_t* keys, int cap, int32_t* count, hipStream_t st) {
   hipLaunchKernelGGL(tile_totals_kernel, dim3(ib.ntiles), dim3(kT), 0, st, ib.bitmap, ib.nwords, ib.tiles);
   hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(kT), 0, st, ib.tiles, ib.ntiles, count, cap);
@@ -257,9 +229,7 @@ int scan_and_emit(const IndexBuf& ib, uint32_t* keys, int cap, int32_t* count, h
   return pn::check_launch("sparse index scan");
 }
 
-inline Dims mk(const int32_t* d) { return Dims{d[0], d[1], d[2], d[3]}; }
 inline Geo mkg(const int32_t* k, const int32_t* s, const int32_t* p) { return Geo{{k[0], k[1], k[2]}, {s[0], s[1], s[2]}, {p[0], p[1], p[2]}}; }
-inline uint64_t cells_of(const int32_t* d) { return (uint64_t)d[0] * d[1] * d[2] * d[3]; }
 
 }  // namespace
 

@@ -851,32 +851,37 @@ class VoxelNet(SingleStageDetector):
                  pretrained=None):
         super().__init__(reader, backbone, neck, bbox_head, seg_head, part_head, train_cfg, test_cfg, pretrained)
 
-    def extract_feat_hard(self, data):
-        """voxelnet.py:47-58; returns the NHWC neck output"""
+    def extract_feat_hard(self, data, return_conv1=False):
+        """voxelnet.py:47-58; returns the NHWC neck output (``return_conv1``: and the encoder's level 0, for the voxel seg head)"""
         feats = self.reader(data["features"], data["num_voxels"])
-        x = self.backbone.forward_nhwc(feats, data["coors"], data["batch_size"], data["input_shape"])
-        return self.neck.forward_nhwc(x) if self.with_neck else x
+        x = self.backbone.forward_nhwc(feats, data["coors"], data["batch_size"], data["input_shape"], return_conv1=return_conv1)
+        return self._through_neck(x, return_conv1)
 
-    def extract_feat_dynamic(self, data):
+    def extract_feat_dynamic(self, data, return_conv1=False):
         """voxelnet.py:60-70: dynamic voxel encoder (mean of the points of a voxel) -> sparse backbone on unq"""
         feats, unq = self.reader(data)
-        x = self.backbone.forward_nhwc(feats, unq.to(torch.int32), data["batch_size"], [int(v) for v in data["grid_size"]])
-        return self.neck.forward_nhwc(x) if self.with_neck else x
+        x = self.backbone.forward_nhwc(feats, unq.to(torch.int32), data["batch_size"], [int(v) for v in data["grid_size"]], return_conv1=return_conv1)
+        return self._through_neck(x, return_conv1)
 
-    def _neck_map(self, example):
-        """reference ``example`` dict (hard-voxel or dynamic keys) -> the NHWC neck output"""
+    def _through_neck(self, x, with_level):
+        x, level0 = x if with_level else (x, None)
+        x = self.neck.forward_nhwc(x) if self.with_neck else x
+        return (x, level0) if with_level else x
+
+    def _neck_map(self, example, return_conv1=False):
+        """reference ``example`` dict (hard-voxel or dynamic keys) -> the NHWC neck output (``return_conv1``: and the encoder's level 0)"""
         eval_only(self, "VoxelNet")
         if "voxels" in example:
             hip.require_device(example["voxels"], example["coordinates"])
             data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
                         batch_size=len(example["num_voxels"]), input_shape=[int(v) for v in example["shape"][0]])
-            x = self.extract_feat_hard(data)
+            x = self.extract_feat_hard(data, return_conv1)
         else:
             hip.require_device(example["points"], example["grid_ind"])
             data = dict(points=example["points"], grid_ind=example["grid_ind"], num_points=example["num_points"],
                         batch_size=len(example["num_points"]), voxel_size=example["voxel_size"][0], pc_range=example["pc_range"][0],
                         grid_size=example["grid_size"][0])
-            x = self.extract_feat_dynamic(data)
+            x = self.extract_feat_dynamic(data, return_conv1)
         return x
 
     def forward_two_stage(self, example, return_loss=False, **kwargs):
@@ -892,12 +897,34 @@ class VoxelNet(SingleStageDetector):
         return self.bbox_head(ops.as_nchw(x)), x
 
     def forward(self, example, return_loss=True, **kwargs):
+        if self.seg_head is not None:
+            return self._forward_with_seg(example, return_loss, **kwargs)
         preds = self.bbox_head(ops.as_nchw(self._neck_map(example)))
         if return_loss:
             return self.bbox_head.loss(example, preds)
         if kwargs.get("raw_preds", False) or self.test_cfg is None:
             return preds
         return {"det": self.bbox_head.predict(example, preds, self.test_cfg, **kwargs)}
+
+    def _forward_with_seg(self, example, return_loss, **kwargs):
+        """voxelnet.py:72-131 with a voxel seg head (DeconvConvHead): the head reads the encoder's conv1 level and the neck's output and is
+        evaluated at the active voxels -> {'seg': per-point labels} (+ 'det' with a bbox head: what the seg-less detector returns under
+        that key, the raw maps without a test_cfg).  ``raw_preds``: the heads' own outputs under the two keys.  Inference."""
+        if return_loss:
+            raise NotImplementedError("VoxelNet: return_loss=True with a seg head is not built -- training the voxel segmentation head (its loss and "
+                                      "the backward of the voxel_seg kernels) is the follow-up; call forward(example, return_loss=False)")
+        if not hasattr(self.seg_head, "forward_voxels"):
+            raise NotImplementedError(f"VoxelNet: the seg head {type(self.seg_head).__name__} has no voxel-wise form; DeconvConvHead (height > 1) is the "
+                                      "seg head of the reference's VoxelNet configs")
+        x, level0 = self._neck_map(example, return_conv1=True)
+        seg_preds = self.seg_head.forward_voxels(level0, x)
+        raw = kwargs.get("raw_preds", False)
+        out = {}
+        if self.bbox_head is not None:
+            preds = self.bbox_head(ops.as_nchw(x))
+            out["det"] = preds if (raw or self.test_cfg is None) else self.bbox_head.predict(example, preds, self.test_cfg, **kwargs)
+        out["seg"] = seg_preds if raw else self.seg_head.predict(example, seg_preds, self.test_cfg, device_only=kwargs.get("device_only", False))
+        return out
 
 
 @DETECTORS.register_module

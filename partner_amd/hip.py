@@ -214,6 +214,12 @@ SIGNATURES = {
     "pn_sparse_group_balance": (_I, [_P, _P, _I, _P, _P]),
     "pn_sparse_to_dense_nhwc": (_I, [_P, _P, _I, _P, _P, _I, _P, _P]),
     "pn_sparse_to_dense_index_nhwc": (_I, [_P, _P, _P, _I, _P, _P]),
+    "pn_voxel_seg_class_pad": (_I, [_I]),
+    "pn_voxel_seg_packed_weight_floats": (_SZ, [_I, _I]),
+    "pn_deconv_overlap_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "pn_voxel_seg_logits_f32": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "pn_voxel_seg_point_labels": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "pn_voxel_seg_scatter_labels": (_I, [_P, _I, _P, _I, _P, _I, _P, _P]),
     "pn_assign_heatmap_workspace_bytes": (_SZ, [_I, _I]),
     "pn_assign_heatmap_polar_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "pn_assign_heatmap_cart_sectors_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),

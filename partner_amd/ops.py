@@ -19,4 +19,5 @@ from .ops_deform import *  # noqa: F401,F403
 from .ops_index import *  # noqa: F401,F403
 from .ops_token import *  # noqa: F401,F403
 from .ops_train import *  # noqa: F401,F403
+from .ops_voxel_seg import *  # noqa: F401,F403
 from .routes import R, S  # noqa: F401

@@ -608,3 +608,152 @@ class SingleConvHead(nn.Module):
             ret_dict["seg"].append({token: labels})
             ret_dict["ins"].append({token: ins})
         return ret_dict
+
+
+class VoxelSegPreds:
+    """``DeconvConvHead.forward_voxels``' result: ``logits`` (rows, NCpad) -- row r holds the ``num_classes`` logits of cell ``queries[r]``
+    (an int32 key of ``level.dims``), rows at or beyond ``*count`` are undefined -- and the encoder's ``level`` (ops.SparseLevel) with the
+    up-sampled neck map ``u``, which ``predict`` evaluates further cells from.  ``active``: the queries are the level's active set."""
+
+    def __init__(self, logits, queries, count, level, u, active):
+        self.logits, self.queries, self.count, self.level, self.u, self.active = logits, queries, count, level, u, active
+
+
+@SEG_HEAD.register_module
+class DeconvConvHead(SingleConvHead):
+    """The 3-D segmentation head of the reference's VoxelNet seg configs (seg_head.py:223-264, ``height`` > 1):
+    seg_preds = Conv2d((Cv + 1) D -> NC D, 3x3)(cat[conv1.dense(), deconv(x2)] viewed with the height folded into the channels), viewed as
+    (B, NC, D, H, W).  Parameters as the reference's: ``deconv.weight`` (Cin, D, 2S, 2S), ``conv.weight`` (NC D, (Cv + 1) D, 3, 3),
+    ``conv.bias``.
+
+    The dense form is 3.2 TFLOP and a 1 GB logit tensor per sample at the config's shape, and its output is only read at cells that hold
+    points: the head here evaluates the logits at a LIST of cells (csrc/voxel_seg.hip), by default the encoder's active set.  f32, eval
+    mode, inference."""
+
+    def __init__(self, kernel=3, num_classes=16, in_channels_voxel=16, in_channels=512, up_scale=8, weight=1, loss=None, height=1):
+        # (the reference's ``kernel`` has no default; voxelnet_seg_10sweep.py leaves it out, which the reference cannot build -- 3 is the only form)
+        if height == 1:
+            raise NotImplementedError("DeconvConvHead: height == 1 (the 2-D form, deconvolution to in_channels // up_scale channels) is not built; "
+                                      "the voxel-wise head needs height > 1")
+        if height < 1:
+            raise NotImplementedError(f"DeconvConvHead: height {height}")
+        if kernel != 3:
+            raise NotImplementedError(f"DeconvConvHead: kernel {kernel} is not built -- the voxel-wise logits kernel is the 3x3 form of the reference's configs")
+        if in_channels_voxel != 16:
+            raise NotImplementedError(f"DeconvConvHead: in_channels_voxel {in_channels_voxel} is not built -- the head reads the encoder's 16-channel conv1 level")
+        if not 1 <= num_classes <= 32:
+            raise NotImplementedError(f"DeconvConvHead: num_classes {num_classes} is not built (1..32 are)")
+        if up_scale < 2 or up_scale % 2:
+            raise NotImplementedError(f"DeconvConvHead: up_scale {up_scale} is not built -- the overlap-add kernel takes even scales")
+        super().__init__(kernel, num_classes * height, height + in_channels_voxel * height, weight, loss)
+        self.num_classes, self.height, self.up_scale, self.in_channels_voxel = num_classes, height, up_scale, in_channels_voxel
+        self.deconv = nn.ConvTranspose2d(in_channels, height, kernel_size=2 * up_scale, stride=up_scale, padding=up_scale // 2, bias=False)
+
+    def set_compute_dtype(self, dtype: str):
+        if dtype != "f32":
+            raise NotImplementedError("DeconvConvHead: bf16 is not built -- the voxel-wise head runs in f32 only")
+        return self
+
+    def _build_voxel_plan(self):
+        w, b = self.conv.weight, self.conv.bias
+        packed, pbias = ops.voxel_seg_pack(w, b, self.height, self.num_classes)
+        return dict(deconv=ops.DeconvOverlap(self.deconv.weight, self.up_scale), packed=packed, bias=pbias)
+
+    def _voxel_plan(self, *tensors):
+        if any(t.dtype != torch.float32 for t in tensors):
+            raise NotImplementedError("DeconvConvHead: bf16 is not built -- the voxel-wise head takes f32 tensors")
+        eval_only(self, "DeconvConvHead")
+        hip.require_device(*tensors)
+        return self._plan.get(self, self._build_voxel_plan)
+
+    def forward_nhwc(self, x1, x2):
+        raise NotImplementedError("DeconvConvHead: there is no dense NHWC form -- forward_voxels(level0, x2_nhwc) evaluates the head at voxels")
+
+    @torch.no_grad()
+    def forward_voxels(self, level0, x2_nhwc: torch.Tensor, queries: Optional[torch.Tensor] = None, n_queries: Optional[torch.Tensor] = None) -> VoxelSegPreds:
+        """level0: the encoder's ops.SparseLevel (``SpMiddleResNetFHD.forward_nhwc(..., return_conv1=True)``), x2_nhwc (B, h, w, Cin) the
+        neck's output -> VoxelSegPreds with one logits row per query cell.  ``queries``: int32 keys ((b D + z) H + y) W + x, any cells in
+        any order (``n_queries``: their device count; default all); default: the level's active set, in key order."""
+        plan = self._voxel_plan(level0.feats, x2_nhwc)
+        b, d, h, w = level0.dims
+        if d != self.height:
+            raise ValueError(f"DeconvConvHead: the level is {d} cells high, the head was built with height {self.height}")
+        u = plan["deconv"](x2_nhwc)
+        if tuple(u.shape) != (b, h, w, d):
+            raise ValueError(f"DeconvConvHead: the up-sampled neck map is {tuple(u.shape[1:3])}, the voxel level {(h, w)} -- up_scale {self.up_scale} does not "
+                             "match the encoder's down-sampling")
+        active = queries is None
+        if active:
+            queries, n_queries = level0.keys, level0.count
+        logits = ops.voxel_seg_logits(level0, u, plan["packed"], plan["bias"], self.num_classes, queries, n_queries)
+        return VoxelSegPreds(logits, queries, n_queries, level0, u, active)
+
+    @torch.no_grad()
+    def forward(self, x1, x2):
+        """logical dense tensors as the reference's signature (seg_head.py:251-264): x1 (B, 16, D, H, W) = ``conv1.dense()``, x2 (B, Cin, h, w)
+        -> {'seg_preds': (B, NC, D, H, W)}.  The SMALL-SHAPE PARITY PATH: it builds the site index from the nonzero sites of x1 (a host
+        read-back) and queries EVERY cell, which is the dense cost the voxel form exists to avoid; the detector uses ``forward_voxels``."""
+        if x1.dim() != 5:
+            raise NotImplementedError("DeconvConvHead: a 4-D x1 is the height == 1 form, which is not built")
+        self._voxel_plan(x1, x2)
+        level = ops.sparse_level_from_dense(x1)
+        b, d, h, w = level.dims
+        cells = torch.arange(b * d * h * w, dtype=torch.int32, device=x1.device)
+        preds = self.forward_voxels(level, ops.to_nhwc(x2), cells)
+        return {"seg_preds": preds.logits.view(b, d, h, w, -1)[..., :self.num_classes].permute(0, 4, 1, 2, 3)}
+
+    def loss(self, example, preds_dicts, **kwargs):
+        raise NotImplementedError("DeconvConvHead.loss: training the voxel segmentation head (sparse cross-entropy + Lovasz over the labelled voxels and the "
+                                  "backward of the three voxel_seg kernels) is not built; it is the follow-up of the voxel-wise head")
+
+    def predict_panoptic(self, *args, **kwargs):
+        raise NotImplementedError("DeconvConvHead.predict_panoptic: panoptic fusion on voxel predictions is not built")
+
+    def predict_panoptic_sweep(self, *args, **kwargs):
+        raise NotImplementedError("DeconvConvHead.predict_panoptic_sweep: panoptic fusion on voxel predictions is not built")
+
+    @torch.no_grad()
+    def predict(self, example, preds_dicts, test_cfg=None, device_only=False, **kwargs):
+        """per-point semantic labels (seg_head.py:170-192, the 5-D branch): 1 + argmax over the classes at every point's cell
+        ``example['valid_grid_ind'][i]`` (n_i, 3) [z, y, x], ties to the lowest class.  ``preds_dicts``: ``forward_voxels``' result over the
+        active set (or {'seg_preds': that}).  A point whose cell is no active site (hard voxelization dropped its voxel) gets the label of
+        that cell's own logits, from a second launch over those cells; nothing is read back for it.
+        -> list of {token: labels (n_i,) int64}, or with ``device_only`` the flat (rows,) int64 tensor in row order."""
+        preds = preds_dicts["seg_preds"] if isinstance(preds_dicts, dict) else preds_dicts
+        if not isinstance(preds, VoxelSegPreds) or not preds.active:
+            raise TypeError("DeconvConvHead.predict takes the VoxelSegPreds of forward_voxels over the level's active set")
+        plan = self._voxel_plan(preds.logits)
+        lv = preds.level
+        bsz = lv.dims[0]
+        gi, offs, acc = self._point_rows(example, bsz, preds.logits.device)
+
+        def miss_logits(keys, count):
+            return ops.voxel_seg_logits(lv, preds.u, plan["packed"], plan["bias"], self.num_classes, keys, count)
+
+        labels = ops.voxel_seg_point_labels(preds.logits, lv, self.num_classes, gi, offs, miss_logits)
+        if device_only:
+            return labels
+        if acc is None:
+            raise ValueError("DeconvConvHead.predict: per-sample lists need example['valid_grid_ind'] as a list; a flat tensor gives device_only=True")
+        metas = example.get("metadata", list(range(bsz)))
+        return [{sample_token(metas, i): labels[acc[i]:acc[i + 1]]} for i in range(bsz)]
+
+    @staticmethod
+    def _point_rows(example, bsz, dev):
+        """``example['valid_grid_ind']`` -- the per-sample list of (n_i, 3) [z, y, x] device tensors, or ONE (rows, 3) tensor with
+        ``example['point_offsets']`` (B + 1,) int32 on the device -> (rows int64, offsets, host prefix sums or None).  The counts come from
+        the list itself: in a hard-voxel ``example`` ``num_points`` counts the points of a voxel, not of a sample."""
+        gi = example["valid_grid_ind"]
+        if torch.is_tensor(gi):
+            offs = example.get("point_offsets")
+            if offs is None:
+                raise ValueError("DeconvConvHead.predict: a flat valid_grid_ind tensor needs example['point_offsets']")
+            hip.require_device(gi, offs)
+            assert offs.dtype == torch.int32 and offs.dim() == 1 and offs.is_contiguous() and offs.shape[0] == bsz + 1, \
+                "point_offsets must be a contiguous int32 (B + 1,) tensor"
+            return gi.to(torch.int64).contiguous(), offs, None
+        assert len(gi) == bsz, "valid_grid_ind must hold one tensor per sample"
+        hip.require_device(*gi)
+        acc = prefix_sums([int(g.shape[0]) for g in gi])
+        rows = torch.cat([g.to(torch.int64).view(-1, 3) for g in gi], 0).contiguous()
+        return rows, torch.tensor(acc, dtype=torch.int32, device=dev), acc

@@ -154,9 +154,12 @@ class SpMiddleResNetFHD(nn.Module):
                  (C.c_int32 * 4)(*in_dims), self._i3(geo[0]), self._i3(geo[1]), self._i3(geo[2]), nbr.data_ptr(), hip.stream())
         return nbr
 
-    def forward_nhwc(self, voxel_features: torch.Tensor, coors: torch.Tensor, batch_size: int, input_shape, n_voxels: torch.Tensor = None):
+    def forward_nhwc(self, voxel_features: torch.Tensor, coors: torch.Tensor, batch_size: int, input_shape, n_voxels: torch.Tensor = None,
+                     return_conv1: bool = False):
         """voxel_features (V,C) f32, coors (V,4) int [b,z,y,x], input_shape [x,y,z] -> NHWC (B, H', W', 128*D') dense BEV map.
-        ``n_voxels``: optional device int32 count (rows beyond it are ignored); no host synchronisation inside."""
+        ``n_voxels``: optional device int32 count (rows beyond it are ignored); no host synchronisation inside.
+        ``return_conv1``: -> (map, ops.SparseLevel of level 0 with the ``conv1`` features (cap, 16) in key order): what the reference hands
+        the voxel segmentation head as ``multi_scale_voxel_features['conv1']`` (scn.py:174,186-191).  The buffers exist either way."""
         eval_only(self, "SpMiddleResNetFHD")
         hip.require_device(voxel_features, coors)
         lib = hip.load()
@@ -276,6 +279,7 @@ class SpMiddleResNetFHD(nn.Module):
         wait(cur)
         x = self._conv(feats, cur["cap"], cur["nbr"], cur["count"], cur["cap"], plan["input"], ops.ACT_RELU)
         li = 0
+        conv1 = None
         for stage in plan["stages"]:
             if stage["down"] is not None:
                 li += 1
@@ -286,6 +290,8 @@ class SpMiddleResNetFHD(nn.Module):
             for c1, c2 in stage["blocks"]:
                 y = self._conv(x, cur["cap"], cur["nbr"], cur["count"], cur["cap"], c1, ops.ACT_RELU, groups=cur["grp"])
                 x = self._conv(y, cur["cap"], cur["nbr"], cur["count"], cur["cap"], c2, ops.ACT_RELU, residual=x, groups=cur["grp"])
+            if li == 0 and return_conv1:
+                conv1 = ops.SparseLevel(feats=x, index=cur["index"], keys=cur["keys"], count=cur["count"], cap=cur["cap"], dims=list(cur["dims"]))
         last = levels[li + 1]
         wait(last)
         x = self._conv(x, cur["cap"], last["dnbr"], last["count"], last["cap"], plan["extra"], ops.ACT_RELU, groups=last["dgrp"])
@@ -297,7 +303,7 @@ class SpMiddleResNetFHD(nn.Module):
         else:
             hip.call("pn_sparse_to_dense_nhwc", x.data_ptr(), last["keys"].data_ptr(), last["cap"], last["count"].data_ptr(), (C.c_int32 * 4)(*odims), cch,
                      out.data_ptr(), st)
-        return out
+        return (out, conv1) if return_conv1 else out
 
     @staticmethod
     def _mark(side):
