@@ -788,6 +788,8 @@ int pn_center_loss_fwd(const float *hm_logits, int hm_pixel_stride, const float 
  * for a mean over ranks, or 1).  d_hm (B,H,W,d_hm_pixel_stride) and d_box_ptrs[i]
  * (B,H,W,d_box_pixel_strides[i]) are fully overwritten (zeros where no gradient flows, including
  * pad channels), so they can feed the MFMA data/weight-gradient kernels directly.
+ * Each d_box buffer is a map of its own (its whole extent is zero-filled), not a channel slice of a
+ * shared one.  max_objs <= 1024 (the forward takes any).  A refused call writes nothing.
  * Objects that share a cell are folded in object order: bitwise reproducible. */
 int pn_center_loss_bwd(const float *hm_logits, int hm_pixel_stride, const float *hm_target, int batch,
                        int classes, int h, int w, const float *const *box_ptrs,

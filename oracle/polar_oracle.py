@@ -405,7 +405,7 @@ def _gather_at(feat: Tensor, ind: Tensor) -> Tensor:
 def center_loss(preds: Dict[str, Tensor], hm_t: Tensor, ind: Tensor, mask: Tensor, cat: Tensor, anno_box: Tensor,
                 code_weights: Sequence[float], weight: float):
     hm = torch.clamp(torch.sigmoid(preds["hm"]), min=1e-4, max=1 - 1e-4)
-    m = mask.float()
+    m = mask.to(hm.dtype)  # mask.float() for float32 predictions; float64 ones keep num_pos + 1e-4 in float64
     neg = (torch.log(1 - hm) * hm ** 2 * (1 - hm_t) ** 4).sum()
     pos_pred = _gather_at(hm, ind).gather(2, cat[:, :, None])
     pos = (torch.log(pos_pred) * (1 - pos_pred) ** 2 * m[:, :, None]).sum()

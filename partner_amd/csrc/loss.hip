@@ -1,9 +1,13 @@
-// CenterPoint loss, forward value.
+// CenterPoint loss, forward value and backward.
 // Reference: CenterHead.loss / _sigmoid  det3d/models/bbox_heads/center_head.py:244-288,
 //            FastFocalLoss / RegLoss     det3d/models/losses/centernet_loss.py:26-54, 6-24,
 //            _transpose_and_gather_feat  det3d/core/utils/center_utils.py:66-80
 // Two launches: (1) the dense negative focal term, fp64 block partials; (2) one block folds the
 // partials in a fixed order and adds the <= B*max_objs positive / box terms.  Deterministic.
+// The forward takes any max_objs; the backward keeps a sample's live objects in a 1024-entry LDS list and refuses max_objs > 1024.
+// The backward writes every float of its gradient buffers: d_hm (all d_hm_pixel_stride channels of every cell) by the dense kernel,
+// each d_box buffer by a zero fill of its whole (B,H,W,pixel stride) extent before the sparse kernel -- so a d_box buffer is a map of
+// its own, not a channel slice of a shared one.  A refused call queues nothing (tests/test_hip_center_loss.py).
 #include "pn_common.h"
 #include <algorithm>
 
@@ -272,12 +276,12 @@ int pn_center_loss_bwd(const float* hm_logits, int hm_pixel_stride, const float*
     bd.p[i] = i < n_box_src ? d_box_ptrs[i] : nullptr;
     bd.ps[i] = i < n_box_src ? d_box_pixel_strides[i] : 0;
     tot += bs.nch[i];
-    if (i < n_box_src) {
-      PN_REQUIRE(bd.p[i] && bd.ps[i] >= bs.nch[i], "center_loss_bwd: bad gradient buffer for a box source");
-      if (int rc = pn::zero_async(bd.p[i], (size_t)batch * h * w * bd.ps[i] * sizeof(float), pn::S(stream))) return rc;
-    }
+    if (i < n_box_src) PN_REQUIRE(bd.p[i] && bd.ps[i] >= bs.nch[i], "center_loss_bwd: bad gradient buffer for a box source");
   }
   PN_REQUIRE(tot == box_dims, "center_loss_bwd: box sources do not add up to box_dims");
+  // nothing is queued before every argument has been accepted: a refused call leaves the gradient buffers untouched
+  for (int i = 0; i < n_box_src; ++i)
+    if (int rc = pn::zero_async(bd.p[i], (size_t)batch * h * w * bd.ps[i] * sizeof(float), pn::S(stream))) return rc;
   for (int d = 0; d < 16; ++d) bs.sel[d] = d < box_dims ? anno_sel[d] : 0;
   const size_t total = (size_t)batch * h * w * d_hm_pixel_stride;
   hipLaunchKernelGGL(focal_neg_bwd_kernel, dim3((unsigned)std::min<size_t>(4096, (total + 255) / 256)), dim3(256), 0, pn::S(stream),

@@ -316,7 +316,8 @@ def _loss_common(hm: torch.Tensor, ncls: int, boxes, tg: CenterLossTargets, code
 
 def center_loss(hm: torch.Tensor, ncls: int, boxes, tg: CenterLossTargets, code_weights, weight: float, with_vel=True):
     """hm: NHWC logits (B,H,W,>=ncls); boxes: [(NHWC tensor, channels)] in the reference order
-    (reg, height, dim[, vel], rot).  -> out[4+ndim] = [det, hm, loc, num_pos, elem...] (device)"""
+    (reg, height, dim[, vel], rot); hm and the box tensors may be channel slices of wider NHWC maps.  Any number of object slots.
+    -> out[4+ndim] = [det, hm, loc, num_pos, elem...] (device)"""
     hip.require_device(hm)
     lib = hip.load()
     args, ndim, cw = _loss_common(hm, ncls, boxes, tg, code_weights, with_vel)
@@ -329,7 +330,9 @@ def center_loss(hm: torch.Tensor, ncls: int, boxes, tg: CenterLossTargets, code_
 
 def center_loss_bwd(hm: torch.Tensor, ncls: int, boxes, tg: CenterLossTargets, code_weights, weight: float, fwd_out: torch.Tensor,
                     grad_scale=1.0, with_vel=True, d_hm: Optional[torch.Tensor] = None, d_boxes=None):
-    """-> (d_hm, [d_box...]) NHWC, channel counts padded to multiples of 4 (pad channels zero)"""
+    """-> (d_hm, [d_box...]) NHWC, channel counts padded to multiples of 4 (pad channels zero).  ``d_hm`` / ``d_boxes``: contiguous
+    (B,H,W,stride >= channels) buffers of the caller's, one per source; every float of them is overwritten (zeros in the channels past
+    the real ones and in box cells without a live object).  At most 1024 object slots per sample (the forward has no such limit)."""
     hip.require_device(hm)
     args, ndim, cw = _loss_common(hm, ncls, boxes, tg, code_weights, with_vel)
     b, h, w, _ = hm.shape
