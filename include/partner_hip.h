@@ -1366,10 +1366,10 @@ int pn_transpose_hw_f32(const float *in, int b, int h, int w, int c, float *out,
  * branches (RangeStratified 'reg', grouped 'rot_vel', 'height', 'dim', 'hm') and their last convolutions
  * (det3d/models/bbox_heads/center_head_parallel.py:120-196, 262-284; det3d/models/utils/norm.py:58-75).
  *   desc / in / packed_w / scale / shift / out: as pn_conv2d_nhwc_f32 (range_strata > 1 and groups > 1 become z slices).
- *   stat_*: statistics of the affine-applied, pre-activation output (desc.act must be PN_ACT_NONE for them to be the
- *     norm's input): stat_partials (pn_conv_stat_partial_floats floats of scratch), stat_strata (RSNorm on a plain convolution: strata along the output width, each a multiple
+ *   stat_*: statistics of the affine-applied output, which is the map the job writes: desc.act must be PN_ACT_NONE (a
+ *     statistics job with an activation is refused): stat_partials (pn_conv_stat_partial_floats floats of scratch), stat_strata (RSNorm on a plain convolution: strata along the output width, each a multiple
  *     of 32 columns; 1 otherwise -- the stratified convolution's strata are its z slices), stat_channel_groups (1: one group
- *     over all columns; cout: per channel), stat_gamma / stat_beta ([stratum][cout]), stat_eps;
+ *     over all columns; cout: per channel, with stat_strata = 1 only), stat_gamma / stat_beta ([stratum][cout]), stat_eps;
  *     outputs (written by pn_conv_stats_finalize_f32): stat_affine [batch][stat_affine_strata][cout][2] = (A, B) with y = x*A + B  and / or
  *              stat_mean_rstd [batch][stat_affine_strata][groups][2] (the layout pn_groupnorm_apply_f32 reads).
  *   norm_*: normalise-on-load: input element (b, ih, iw, c) is read as relu(x*A + B), (A, B) =

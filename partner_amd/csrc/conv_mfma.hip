@@ -78,8 +78,8 @@ struct ConvArgs {
   // epilogue's LDS tiles hold whole map rows (BM % OW == 0), so a quad's neighbour pixels are in the block
   float* planes;
   unsigned plane_floats;
-  // ---- statistics of the (affine-applied, pre-activation) output for the GroupNorm-family layer that follows
-  // (st_part != null).  Every block writes ONE partial (sum, sum of squares) per column and tile (per-channel groups) or per
+  // ---- statistics of the affine-applied output for the GroupNorm-family layer that follows (st_part != null; such a job
+  // has act == NONE, so this is the map it writes).  Every block writes ONE partial (sum, sum of squares) per column and tile (per-channel groups) or per
   // 32-row segment and wave column (all-channel groups); conv_stats_finalize_kernel (a separate small launch: folding them
   // inside this kernel costs registers, i.e. occupancy, in every variant) adds them in a fixed order and writes the affine
   // table the consumer applies while it loads its input tile.
@@ -551,7 +551,8 @@ __device__ __forceinline__ void conv_body(const ConvArgs& a, const int bid, cons
       }
     }
     if (a.st_part) {
-      // ---- output statistics, reduced inside the block before they leave it:
+      // ---- output statistics, reduced inside the block before they leave it.  They are taken of acc * scale + shift, which IS the
+      // map written above: job_to_args refuses a statistics job with an activation (and residuals do not exist on that path).
       //   per-channel groups: ONE (sum, sum of squares) per column for the whole tile (the host guarantees a tile never
       //                       straddles two samples)              -> part[z][tile][cout_pad]
       //   all-channel groups: one pair per 32-row segment and wave column (lanes reduced by the xor butterfly)
@@ -2250,6 +2251,7 @@ static int job_to_args(const pn_conv_job& jb, int tile, ConvArgs& a, size_t& ext
   a.st_segs_z = a.nmt * (bm / 32);
   if (jb.stat_partials) {
     PN_REQUIRE(a.mode != MODE_DECONV2, "conv_multi: no statistics for the transposed convolution");
+    PN_REQUIRE(a.act == PN_ACT_NONE, "conv_multi: a statistics job takes no activation (the statistics are those of the map it writes)");
     PN_REQUIRE((a.Cout % 4 == 0) && (a.out_ps % 4 == 0) && (a.out_co % 4 == 0) && (((uintptr_t)a.out & 15) == 0),
                "conv_multi: statistics need the vectorised epilogue (channel counts / offsets multiples of 4)");
     PN_REQUIRE(a.mode == MODE_STRAT || zdim == 1, "conv_multi: statistics of grouped convolutions are not supported");
@@ -2260,6 +2262,7 @@ static int job_to_args(const pn_conv_job& jb, int tile, ConvArgs& a, size_t& ext
     PN_REQUIRE(a.B == 1 || (a.OH * a.OWsub) % (jb.stat_channel_groups > 1 ? bm : 32) == 0,
                "conv_multi: with batch > 1 a sample must be a whole number of tiles (per-channel statistics) / 32-row segments");
     PN_REQUIRE(jb.stat_channel_groups == 1 || jb.stat_channel_groups == a.ncols, "conv_multi: channel groups must be 1 or the column count");
+    PN_REQUIRE(S == 1 || jb.stat_channel_groups == 1, "conv_multi: stat_strata needs all-channel groups (the per-channel fold has no strata)");
     const int slots = a.mode == MODE_STRAT ? zdim : S;
     PN_REQUIRE(jb.stat_affine_strata >= slots, "conv_multi: stat_affine_strata too small");
     a.st_part = jb.stat_partials; a.st_S = S; a.st_cg = jb.stat_channel_groups;
