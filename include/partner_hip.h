@@ -1055,7 +1055,10 @@ int pn_panoptic_points_sweep_f32(const float *seg, long long sample_stride, int 
  * features live in key order, key = ((b*D+z)*H+y)*W+x.  All counts stay on the device.
  *   pn_sparse_index_from_coords   coords (n,4) int32 [b,z,y,x] -> index, keys (rank order), count, and the rank of
  *                                 every input row (pn_sparse_permute_rows then puts the features in key order)
- *   pn_sparse_index_downsample    active output sites of a strided SparseConv3d (kernel/stride/pad per axis z,y,x)
+ *   pn_sparse_index_downsample    active output sites of a strided SparseConv3d (kernel/stride/pad per axis z,y,x).  With more
+ *                                 active sites than out_capacity: *out_count = out_capacity, out_keys holds the first out_capacity
+ *                                 keys (ascending) and nothing behind them is written; the index itself stays complete (every
+ *                                 active cell keeps its true rank, also ranks >= out_capacity) -- only the key list is cut
  *   pn_sparse_neighbors           nbr[out site][tap] = input index or -1; tap = (kz*KH + ky)*KW + kx; one table
  *                                 serves every convolution that shares an indice_key
  *   pn_sparse_conv_f32            out = act((sum_t W_t in[nbr[.][t]]) * scale + shift + residual), on the MFMA

@@ -10,7 +10,11 @@ constexpr int kT = 256, kItems = 8, kTile = kT * kItems;  // words per scan tile
 
 struct Dims { int B, D, H, W; };
 
-__device__ __forceinline__ uint32_t make_key(const Dims& d, int b, int z, int y, int x) { return (uint32_t)(((b * d.D + z) * d.H + y) * d.W + x); }
+// (unsigned arithmetic: the entry points admit grids of up to 2^32 cells, and a key past 2^31 must not be a signed overflow; callers pass
+// coordinates inside the grid)
+__device__ __forceinline__ uint32_t make_key(const Dims& d, int b, int z, int y, int x) {
+  return (((uint32_t)b * (uint32_t)d.D + (uint32_t)z) * (uint32_t)d.H + (uint32_t)y) * (uint32_t)d.W + (uint32_t)x;
+}
 
 __device__ __forceinline__ void split_key(const Dims& d, uint32_t key, int& b, int& z, int& y, int& x) {
   x = key % d.W; key /= d.W;
