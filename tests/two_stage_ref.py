@@ -101,24 +101,32 @@ def cells_of(points: torch.Tensor, pc_start=PC_START, voxel_size=VOXEL_SIZE, out
     return ((points[..., 0] - pc_start[0]) / voxel_size[0] / out_stride, (points[..., 1] - pc_start[1]) / voxel_size[1] / out_stride)
 
 
-def sample_map(im: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-    """(H, W, C) map, (n,) coordinates -> (n, C): floor, the four indices clamped to the map, the weights formed from the CLAMPED indices"""
+def sample_map(im: torch.Tensor, x: torch.Tensor, y: torch.Tensor, magnitude=False) -> torch.Tensor:
+    """(H, W, C) map, (n,) coordinates -> (n, C): floor, the four indices clamped to the map, the weights formed from the CLAMPED indices;
+    in the dtype of its arguments.  ``magnitude``: the sum of the four products' absolute values (the scale of what cancels when a
+    point lies outside the map)"""
     h, w = im.shape[:2]
+    f = lambda i: i.to(x.dtype)      # noqa: E731
     x0, y0 = torch.floor(x).long(), torch.floor(y).long()
     x1, y1 = (x0 + 1).clamp(0, w - 1), (y0 + 1).clamp(0, h - 1)
     x0, y0 = x0.clamp(0, w - 1), y0.clamp(0, h - 1)
-    wa, wb = (x1.float() - x) * (y1.float() - y), (x1.float() - x) * (y - y0.float())
-    wc, wd = (x - x0.float()) * (y1.float() - y), (x - x0.float()) * (y - y0.float())
-    return ((im[y0, x0] * wa[:, None] + im[y1, x0] * wb[:, None]) + im[y0, x1] * wc[:, None]) + im[y1, x1] * wd[:, None]
+    wa, wb = (f(x1) - x) * (f(y1) - y), (f(x1) - x) * (y - f(y0))
+    wc, wd = (x - f(x0)) * (f(y1) - y), (x - f(x0)) * (y - f(y0))
+    ta, tb, tc, td = im[y0, x0] * wa[:, None], im[y1, x0] * wb[:, None], im[y0, x1] * wc[:, None], im[y1, x1] * wd[:, None]
+    if magnitude:
+        ta, tb, tc, td = ta.abs(), tb.abs(), tc.abs(), td.abs()
+    return ((ta + tb) + tc) + td
 
 
-def gather(boxes, scores, labels, counts, bev, num_point, code_size, max_rois, pc_start=PC_START, voxel_size=VOXEL_SIZE, out_stride=OUT_STRIDE):
-    """pn_roi_bev_gather_f32 -> rois (B, max_rois, code_size), roi_scores, roi_labels (int64, label + 1), roi_features (B, max_rois, P * C)"""
+def gather(boxes, scores, labels, counts, bev, num_point, code_size, max_rois, pc_start=PC_START, voxel_size=VOXEL_SIZE, out_stride=OUT_STRIDE,
+           magnitude=False):
+    """pn_roi_bev_gather_f32 -> rois (B, max_rois, code_size), roi_scores, roi_labels (int64, label + 1), roi_features (B, max_rois, P * C),
+    evaluated in the dtype of ``boxes`` and ``bev`` (float32 as the kernel, or float64)"""
     b, _, cols = boxes.shape
-    c = bev.shape[-1]
-    assert cols == code_size
-    rois, rs = torch.zeros((b, max_rois, code_size)), torch.zeros((b, max_rois))
-    rl, feat = torch.zeros((b, max_rois), dtype=torch.int64), torch.zeros((b, max_rois, num_point * c))
+    c, dt = bev.shape[-1], boxes.dtype
+    assert cols == code_size and bev.dtype == dt
+    rois, rs = torch.zeros((b, max_rois, code_size), dtype=dt), torch.zeros((b, max_rois), dtype=scores.dtype)
+    rl, feat = torch.zeros((b, max_rois), dtype=torch.int64), torch.zeros((b, max_rois, num_point * c), dtype=dt)
     for i in range(b):
         n = int(counts[i])
         if n == 0:
@@ -127,7 +135,7 @@ def gather(boxes, scores, labels, counts, bev, num_point, code_size, max_rois, p
         rois[i, :n] = bx[:, [0, 1, 2, 3, 4, 5, 8, 6, 7]] if code_size == 9 else bx
         rs[i, :n], rl[i, :n] = scores[i, :n], labels[i, :n] + 1
         x, y = cells_of(box_points(bx, num_point), pc_start, voxel_size, out_stride)      # (n, P)
-        feat[i, :n] = sample_map(bev[i], x.reshape(-1), y.reshape(-1)).reshape(n, num_point * c)
+        feat[i, :n] = sample_map(bev[i], x.reshape(-1), y.reshape(-1), magnitude).reshape(n, num_point * c)
     return rois, rs, rl, feat
 
 
@@ -152,7 +160,8 @@ def roi_head_rows(sd, feats: torch.Tensor, prefix=""):
 
 
 def refine(rois, roi_scores, roi_labels, counts, rcnn_cls, rcnn_reg):
-    """pn_roi_refine_f32 -> boxes (B, max_rois, code_size) in the head's order, scores, labels, counts; rows at or past the count zero"""
+    """pn_roi_refine_f32 -> boxes (B, max_rois, code_size) in the head's order, scores, labels, counts; rows at or past the count zero
+    (whatever the inputs hold there).  Evaluated in the dtype of its arguments"""
     b, r, cs = rois.shape
     reg, cls = rcnn_reg.reshape(b, r, cs), rcnn_cls.reshape(b, r)
     s, c = torch.sin(rois[..., 6]), torch.cos(rois[..., 6])
@@ -164,7 +173,8 @@ def refine(rois, roi_scores, roi_labels, counts, rcnn_cls, rcnn_reg):
     scores = torch.sqrt(torch.sigmoid(cls) * roi_scores)
     labels = roi_labels - 1
     live = torch.arange(r)[None, :] < counts.long()[:, None]
-    return out * live[..., None], scores * live, labels * live, counts.clone()
+    return (torch.where(live[..., None], out, torch.zeros_like(out)), torch.where(live, scores, torch.zeros_like(scores)),
+            torch.where(live, labels, torch.zeros_like(labels)), counts.clone())
 
 
 def second_stage(sd, dets, bev, num_point, code_size, max_rois, pc_start, voxel_size, out_stride, prefix="roi_head."):

@@ -215,8 +215,10 @@ def py_mod(a: torch.Tensor, b: float) -> torch.Tensor:
     return torch.remainder(a, b)
 
 
-def targets(inp, cfg, max_overlaps=None, gt_assignment=None):
-    """pn_roi_max_iou3d_f32 + pn_roi_sample_targets_f32 -> the targets dict (float32 / int64 / int32 torch tensors)"""
+def targets(inp, cfg, max_overlaps=None, gt_assignment=None, dtype=torch.float32):
+    """pn_roi_max_iou3d_f32 + pn_roi_sample_targets_f32 -> the targets dict (float32 / int64 / int32 torch tensors).  ``dtype``: the
+    arithmetic of the two computed outputs, gt_of_rois and rcnn_cls_labels (float64: the same restatement on the same float32 inputs,
+    thresholds and constants); the selection and the copied rows do not depend on it"""
     rois, labels, scores, feats, gt = inp["rois"], inp["roi_labels"], inp["roi_scores"], inp["roi_features"], inp["gt"]
     b, _, cs = rois.shape
     if max_overlaps is None:
@@ -225,8 +227,10 @@ def targets(inp, cfg, max_overlaps=None, gt_assignment=None):
     take = lambda t: torch.stack([t[i][inds[i]] for i in range(b)])      # noqa: E731
     s_rois, iou = take(rois), take(max_overlaps)
     src = torch.stack([gt[i][gt_assignment[i].long()[inds[i]]] for i in range(b)])
-    c32 = lambda v: torch.tensor(v, dtype=torch.float32)      # noqa: E731  (a Python double rounded to f32 once)
+    c32 = lambda v: torch.tensor(v, dtype=torch.float32).to(dtype)      # noqa: E731  (a Python double rounded to f32 once)
     two_pi, pi, half_pi, three_half_pi = c32(2 * math.pi), c32(math.pi), c32(math.pi * 0.5), c32(math.pi * 1.5)
+    rois_out, src_out, iou_out = s_rois, src, iou
+    s_rois, src, iou = s_rois.to(dtype), src.to(dtype), iou.to(dtype)
     ry = s_rois[..., 6] - torch.floor(s_rois[..., 6] / two_pi + 0.5) * two_pi
     enc = src.clone()
     d = src[..., :3] - s_rois[..., :3]
@@ -242,17 +246,17 @@ def targets(inp, cfg, max_overlaps=None, gt_assignment=None):
     h = torch.where(flip, py_mod(h + pi, two_pi), h)
     h = torch.where(h > pi, h - two_pi, h)
     enc[..., 6] = torch.clamp(h, -half_pi, half_pi)
-    f = lambda v: torch.tensor(v, dtype=torch.float32)      # noqa: E731
+    f = lambda v: torch.tensor(v, dtype=torch.float32).to(dtype)      # noqa: E731
     fgt, bgt = f(cfg["CLS_FG_THRESH"]), f(cfg["CLS_BG_THRESH"])
     if cfg["CLS_SCORE_TYPE"] == "roi_iou":
-        lab = (iou > fgt).float()
+        lab = (iou > fgt).to(dtype)
         mid = ~(iou > fgt) & ~(iou < bgt)
         lab = torch.where(mid, (iou - bgt) / f(cfg["CLS_FG_THRESH"] - cfg["CLS_BG_THRESH"]), lab)
     else:
-        lab = (iou > fgt).float()
+        lab = (iou > fgt).to(dtype)
         lab = torch.where((iou > bgt) & (iou < fgt), torch.full_like(lab, -1.0), lab)
-    return dict(sampled_inds=inds.int(), rois=s_rois, roi_labels=take(labels), roi_scores=take(scores), gt_iou_of_rois=iou, roi_features=take(feats),
-                gt_of_rois_src=src, gt_of_rois=enc, reg_valid_mask=(iou > f(cfg["REG_FG_THRESH"])).long(), rcnn_cls_labels=lab,
+    return dict(sampled_inds=inds.int(), rois=rois_out, roi_labels=take(labels), roi_scores=take(scores), gt_iou_of_rois=iou_out, roi_features=take(feats),
+                gt_of_rois_src=src_out, gt_of_rois=enc, reg_valid_mask=(iou > f(cfg["REG_FG_THRESH"])).long(), rcnn_cls_labels=lab,
                 max_overlaps=max_overlaps, gt_assignment=gt_assignment)
 
 
