@@ -1158,6 +1158,44 @@ int pn_voxel_seg_point_labels(const float *rows, int num_classes, const void *in
 int pn_voxel_seg_scatter_labels(const float *rows, int num_classes, const int32_t *dest, int capacity, const int32_t *n_dev, int n_labels,
                                 int64_t *labels, pn_stream_t stream);
 
+/* Training the voxel-wise head (csrc/voxel_seg.hip): the head is evaluated at the LABELLED cells and its backward runs over that list.
+ * f32, no float atomics: two runs give the same bits.  `queries` below is a list of UNIQUE keys in strictly ASCENDING order (the list of
+ * pn_voxel_seg_label_queries and a level's active set both are); dlogits holds one row of NCpad floats per query.
+ *   pn_voxel_seg_label_queries  the targets of seg_heads/seg_head.py:86-96 (get_labels, seg_head.py:30-32: equal shapes -> labels - 1, and
+ *                               SegLoss(ignore = -1), losses/seg_loss.py:19-22, then reads the labelled cells only): labels (B, D, H, W) on
+ *                               the device, label_kind 0 uint8 / 1 int32 / 2 int64 -> keys[i] = ((b D + z) H + y) W + x of the cells whose
+ *                               label is in [1, NC], ascending (the order of flatten_probas, lovasz_losses.py:212-229), out_labels[i] =
+ *                               label - 1, *count = min(labelled cells, capacity), *status = 1 when more cells are labelled than the
+ *                               capacity holds (the list is then the first `capacity` of them; the flag convention of pn_seg_loss_f32's
+ *                               max_valid).  Rows at or beyond *count: out_labels -1, keys 0.  Counts per tile of 1024 cells, one scan,
+ *                               a stable fill; integers only; nothing is read back.
+ *   pn_deconv_overlap_bwd_f32   adjoint of pn_deconv_overlap_f32 (UpsampleShelhamer, seg_head.py:195-212, under autograd):
+ *                               d_cols[b, iy, ix, (ky 2S + kx) D + c] = d_out[b, S iy + ky - S/2, S ix + kx - S/2, c] inside the map, else
+ *                               0.  A pure gather; S even.
+ *   pn_voxel_seg_wgrad_f32      gradients of the packed weights / bias of pn_voxel_seg_logits_f32 (the Conv2d of seg_head.py:246-264
+ *                               under autograd), in the packed layout (every element written, pads zero when dlogits' pad columns are):
+ *                               block (slab, z) walks the queries of its z (two binary searches per sample), 32 at a time.
+ *   pn_voxel_seg_dfeat_f32      d_feats (site_capacity, 16): gradient of the level's conv1 features, one gather per active site and
+ *                               channel over the queries whose 3x3 window holds the site; query_index_buf = a bitmap-rank index
+ *                               (pn_sparse_index_from_coords) over the QUERY cells, whose ranks are the rows of dlogits.  Rows at or
+ *                               beyond *site_n_dev are zero.
+ *   pn_voxel_seg_du_f32         d_u (B, H, W, D): gradient of the up-sampled map, every element written once; exact zeros where no
+ *                               query lies in the pixel's 3x3 column window.
+ * Sums run per z (the forward's slab), then tap, then class, the per-z sums added in z order. */
+size_t pn_voxel_seg_label_queries_workspace_bytes(uint64_t num_cells);
+int pn_voxel_seg_label_queries(const void *labels, int label_kind, const int32_t *dims, int num_classes, int capacity, uint32_t *keys,
+                               int32_t *out_labels, int32_t *count, int32_t *status, void *workspace, size_t workspace_bytes,
+                               pn_stream_t stream);
+int pn_deconv_overlap_bwd_f32(const float *d_out, int batch, int h, int w, int up_scale, int channels, float *d_cols, pn_stream_t stream);
+int pn_voxel_seg_wgrad_f32(const uint32_t *queries, int n_capacity, const int32_t *n_dev, const float *dlogits, const int32_t *dims,
+                           const void *index_buf, const float *feats, const float *u, int num_classes, float *d_packed_w,
+                           float *d_packed_bias, pn_stream_t stream);
+int pn_voxel_seg_dfeat_f32(const uint32_t *site_keys, int site_capacity, const int32_t *site_n_dev, const int32_t *dims,
+                           const void *query_index_buf, int n_query_capacity, const float *dlogits, const float *packed_w, int num_classes,
+                           float *d_feats, pn_stream_t stream);
+int pn_voxel_seg_du_f32(const int32_t *dims, const void *query_index_buf, int n_query_capacity, const float *dlogits, const float *packed_w,
+                        int num_classes, float *d_u, pn_stream_t stream);
+
 /* Backward side of the sparse convolutions (scn.py:97-192 under autograd; spconv's own backward in the reference).
  *   pn_sparse_neighbors_transpose  inv[in row][tap] = the output row that reads it through that tap, or -1 (at most one
  *                                  exists): the data gradient is then pn_sparse_conv_f32 over `inv` with the (Cin, Cout)

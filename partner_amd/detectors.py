@@ -911,8 +911,8 @@ class VoxelNet(SingleStageDetector):
         evaluated at the active voxels -> {'seg': per-point labels} (+ 'det' with a bbox head: what the seg-less detector returns under
         that key, the raw maps without a test_cfg).  ``raw_preds``: the heads' own outputs under the two keys.  Inference."""
         if return_loss:
-            raise NotImplementedError("VoxelNet: return_loss=True with a seg head is not built -- training the voxel segmentation head (its loss and "
-                                      "the backward of the voxel_seg kernels) is the follow-up; call forward(example, return_loss=False)")
+            raise NotImplementedError("VoxelNet: return_loss=True with a seg head is not built on the module -- the voxel segmentation head trains "
+                                      "through train_voxel_seg.VoxelSegTrainStep(model, total_steps).step(example); call forward(example, return_loss=False)")
         if not hasattr(self.seg_head, "forward_voxels"):
             raise NotImplementedError(f"VoxelNet: the seg head {type(self.seg_head).__name__} has no voxel-wise form; DeconvConvHead (height > 1) is the "
                                       "seg head of the reference's VoxelNet configs")

@@ -220,6 +220,12 @@ SIGNATURES = {
     "pn_voxel_seg_logits_f32": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "pn_voxel_seg_point_labels": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "pn_voxel_seg_scatter_labels": (_I, [_P, _I, _P, _I, _P, _I, _P, _P]),
+    "pn_voxel_seg_label_queries_workspace_bytes": (_SZ, [_U64]),
+    "pn_voxel_seg_label_queries": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "pn_deconv_overlap_bwd_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "pn_voxel_seg_wgrad_f32": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "pn_voxel_seg_dfeat_f32": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "pn_voxel_seg_du_f32": (_I, [_P, _P, _I, _P, _P, _I, _P, _P]),
     "pn_assign_heatmap_workspace_bytes": (_SZ, [_I, _I]),
     "pn_assign_heatmap_polar_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "pn_assign_heatmap_cart_sectors_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),

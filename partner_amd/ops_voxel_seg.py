@@ -13,7 +13,8 @@ from . import hip
 from .ops_token import GemmLayer
 
 __all__ = ["SparseLevel", "DeconvOverlap", "sparse_level_from_dense", "voxel_seg_class_pad", "voxel_seg_pack", "voxel_seg_logits",
-           "voxel_seg_point_labels"]
+           "voxel_seg_point_labels", "voxel_seg_label_queries", "voxel_seg_query_index", "voxel_seg_unpack_grads", "voxel_seg_wgrad",
+           "voxel_seg_dfeat", "voxel_seg_du", "deconv_overlap_bwd"]
 
 
 @dataclass
@@ -159,3 +160,130 @@ def voxel_seg_point_labels(rows: torch.Tensor, level: SparseLevel, num_classes: 
         extra = miss_logits(mk, mc)
         hip.call("pn_voxel_seg_scatter_labels", extra.data_ptr(), int(num_classes), mr.data_ptr(), n, mc.data_ptr(), n, labels.data_ptr(), st)
     return labels
+
+
+# ------------------------------------------------------------------------------------------------------------------ training
+def voxel_seg_label_queries(voxel_labels: torch.Tensor, num_classes: int, capacity: int):
+    """the labelled cells of a DEVICE label map (B, D, H, W) or (B, 1, D, H, W), uint8 / int32 / int64, as a query list
+    (seg_head.py:86-96: ``get_labels`` with equal shapes is ``labels - 1`` and 0 becomes the ignored -1)
+    -> (keys (capacity,) int32 ascending, labels - 1 (capacity,) int32 with -1 behind the count, count (1,) int32, status (1,) int32:
+    1 when more cells are labelled than ``capacity`` holds).  Labels outside [1, NC] are ignored.  Nothing is read back."""
+    hip.require_device(voxel_labels)
+    if voxel_labels.dim() == 5 and voxel_labels.shape[1] == 1:
+        voxel_labels = voxel_labels[:, 0]
+    assert voxel_labels.dim() == 4, "voxel_labels must be (B, D, H, W) or (B, 1, D, H, W)"
+    kinds = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}
+    if voxel_labels.dtype not in kinds:
+        raise TypeError(f"voxel_seg_label_queries: labels of {voxel_labels.dtype} -- uint8, int32 and int64 are taken")
+    lab = voxel_labels.contiguous()
+    dims = [int(v) for v in lab.shape]
+    dev, cap = lab.device, int(capacity)
+    assert cap >= 1
+    lib = hip.load()
+    keys = torch.empty(cap, dtype=torch.int32, device=dev)
+    out = torch.empty(cap, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = lib.pn_voxel_seg_label_queries_workspace_bytes(lab.numel())
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    hip.call("pn_voxel_seg_label_queries", lab.data_ptr(), kinds[lab.dtype], _dims(dims), int(num_classes), cap, keys.data_ptr(), out.data_ptr(),
+             count.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, hip.stream())
+    return keys, out, count, status
+
+
+def voxel_seg_query_index(queries: torch.Tensor, n_dev: torch.Tensor, dims) -> torch.Tensor:
+    """bitmap-rank index (``pn_sparse_index_from_coords``) over the cells of an ascending unique query list: the rank of a cell is its row.
+    The keys are split into [b, z, y, x] rows with integer tensor operations (plumbing; the count stays on the device)."""
+    hip.require_device(queries, n_dev)
+    b, d, h, w = (int(v) for v in dims)
+    n = int(queries.shape[0])
+    assert n >= 1 and queries.dtype == torch.int32 and queries.is_contiguous(), "the query list holds at least one row of capacity"
+    k = queries.to(torch.int64) & 0xFFFFFFFF
+    coors = torch.stack([k // (d * h * w), (k // (h * w)) % d, (k // w) % h, k % w], 1).to(torch.int32).contiguous()
+    dev = queries.device
+    index = torch.empty(hip.load().pn_sparse_index_bytes(b * d * h * w), dtype=torch.uint8, device=dev)
+    keys = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    hip.call("pn_sparse_index_from_coords", coors.data_ptr(), n, n_dev.data_ptr(), _dims(dims), index.data_ptr(), keys.data_ptr(), count.data_ptr(),
+             rank.data_ptr(), hip.stream())
+    return index
+
+
+def voxel_seg_unpack_grads(d_packed: torch.Tensor, d_pbias: torch.Tensor, depth: int, num_classes: int):
+    """the inverse of ``voxel_seg_pack`` on gradients: packed [z][slab][tap][16][NCpad] / [z][NCpad] -> the gradients of ``conv.weight``
+    (NC D, 17 D, 3, 3) and ``conv.bias`` (NC D); tensor copies only"""
+    d, nc = int(depth), int(num_classes)
+    dh = (d + 15) // 16
+    gp = d_packed.view(d, d + dh, 9, 16, -1)
+    gw = torch.empty((nc, d, 17, d, 3, 3), dtype=torch.float32, device=gp.device)
+    gw[:, :, :16] = gp[:, :d, :, :, :nc].reshape(d, d, 3, 3, 16, nc).permute(5, 0, 4, 1, 2, 3)
+    gw[:, :, 16] = gp[:, d:, :, :, :nc].reshape(d, dh, 3, 3, 16, nc).permute(5, 0, 1, 4, 2, 3).reshape(nc, d, dh * 16, 3, 3)[:, :, :d]
+    gb = d_pbias.view(d, -1)[:, :nc].t().reshape(nc * d)
+    return gw.view(nc * d, 17 * d, 3, 3), gb.contiguous()
+
+
+def _check_rows(dlogits, queries, num_classes):
+    ncp = voxel_seg_class_pad(num_classes)
+    assert queries.dtype == torch.int32 and queries.dim() == 1 and queries.is_contiguous()
+    assert dlogits.dtype == torch.float32 and dlogits.is_contiguous() and tuple(dlogits.shape) == (int(queries.shape[0]), ncp), \
+        "dlogits must hold one row of NCpad floats per query"
+    return ncp
+
+
+def voxel_seg_wgrad(level: SparseLevel, u: torch.Tensor, queries: torch.Tensor, n_dev: torch.Tensor, dlogits: torch.Tensor, num_classes: int):
+    """-> (d packed weights, d packed bias) of ``voxel_seg_logits`` over an ASCENDING UNIQUE query list"""
+    hip.require_device(level.feats, level.index, u, queries, n_dev, dlogits)
+    b, d, h, w = level.dims
+    ncp = _check_rows(dlogits, queries, num_classes)
+    assert tuple(u.shape) == (b, h, w, d) and u.is_contiguous() and u.dtype == torch.float32
+    assert level.feats.dtype == torch.float32 and level.feats.is_contiguous() and level.feats.shape[1] == 16
+    dh = (d + 15) // 16
+    d_packed = torch.empty((d, d + dh, 9, 16, ncp), dtype=torch.float32, device=u.device)
+    d_pbias = torch.empty((d, ncp), dtype=torch.float32, device=u.device)
+    if queries.shape[0] == 0:
+        return d_packed.zero_(), d_pbias.zero_()
+    hip.call("pn_voxel_seg_wgrad_f32", queries.data_ptr(), int(queries.shape[0]), n_dev.data_ptr(), dlogits.data_ptr(), _dims(level.dims),
+             level.index.data_ptr(), level.feats.data_ptr(), u.data_ptr(), int(num_classes), d_packed.data_ptr(), d_pbias.data_ptr(), hip.stream())
+    return d_packed, d_pbias
+
+
+def voxel_seg_dfeat(level: SparseLevel, query_index: torch.Tensor, dlogits: torch.Tensor, packed_w: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """-> d_feats (rows of ``level.feats``, 16): the gradient of the level's conv1 features; rows at or beyond the level's count are zero"""
+    hip.require_device(level.keys, level.count, query_index, dlogits, packed_w)
+    ncp = voxel_seg_class_pad(num_classes)
+    assert dlogits.dtype == torch.float32 and dlogits.is_contiguous() and dlogits.dim() == 2 and dlogits.shape[1] == ncp
+    rows = int(level.feats.shape[0])
+    assert level.keys.shape[0] >= rows
+    out = torch.empty((rows, 16), dtype=torch.float32, device=dlogits.device)
+    if dlogits.shape[0] == 0:
+        return out.zero_()
+    hip.call("pn_voxel_seg_dfeat_f32", level.keys.data_ptr(), rows, level.count.data_ptr(), _dims(level.dims), query_index.data_ptr(), int(dlogits.shape[0]),
+             dlogits.data_ptr(), packed_w.data_ptr(), int(num_classes), out.data_ptr(), hip.stream())
+    return out
+
+
+def voxel_seg_du(dims, query_index: torch.Tensor, dlogits: torch.Tensor, packed_w: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """-> d_u (B, H, W, D): the gradient of the up-sampled map, every element written"""
+    hip.require_device(query_index, dlogits, packed_w)
+    ncp = voxel_seg_class_pad(num_classes)
+    assert dlogits.dtype == torch.float32 and dlogits.is_contiguous() and dlogits.dim() == 2 and dlogits.shape[1] == ncp
+    b, d, h, w = (int(v) for v in dims)
+    out = torch.empty((b, h, w, d), dtype=torch.float32, device=dlogits.device)
+    if dlogits.shape[0] == 0:
+        return out.zero_()
+    hip.call("pn_voxel_seg_du_f32", _dims(dims), query_index.data_ptr(), int(dlogits.shape[0]), dlogits.data_ptr(), packed_w.data_ptr(), int(num_classes),
+             out.data_ptr(), hip.stream())
+    return out
+
+
+def deconv_overlap_bwd(d_u: torch.Tensor, up_scale: int) -> torch.Tensor:
+    """d_u (B, h S, w S, D) -> d_cols (B h w, 2S 2S D): the adjoint of ``pn_deconv_overlap_f32``"""
+    hip.require_device(d_u)
+    s = int(up_scale)
+    assert d_u.dim() == 4 and d_u.is_contiguous() and d_u.dtype == torch.float32 and d_u.shape[1] % s == 0 and d_u.shape[2] % s == 0
+    b, hh, ww, d = d_u.shape
+    h, w = hh // s, ww // s
+    out = torch.empty((b * h * w, 4 * s * s * d), dtype=torch.float32, device=d_u.device)
+    hip.call("pn_deconv_overlap_bwd_f32", d_u.data_ptr(), b, h, w, s, d, out.data_ptr(), hip.stream())
+    return out

@@ -627,8 +627,8 @@ class DeconvConvHead(SingleConvHead):
     ``conv.bias``.
 
     The dense form is 3.2 TFLOP and a 1 GB logit tensor per sample at the config's shape, and its output is only read at cells that hold
-    points: the head here evaluates the logits at a LIST of cells (csrc/voxel_seg.hip), by default the encoder's active set.  f32, eval
-    mode, inference."""
+    points: the head here evaluates the logits at a LIST of cells (csrc/voxel_seg.hip), by default the encoder's active set.  f32; the
+    module itself is the eval-mode inference form, training runs on the tape at the labelled cells (train_voxel_seg.VoxelSegTrainStep)."""
 
     def __init__(self, kernel=3, num_classes=16, in_channels_voxel=16, in_channels=512, up_scale=8, weight=1, loss=None, height=1):
         # (the reference's ``kernel`` has no default; voxelnet_seg_10sweep.py leaves it out, which the reference cannot build -- 3 is the only form)
@@ -703,8 +703,8 @@ class DeconvConvHead(SingleConvHead):
         return {"seg_preds": preds.logits.view(b, d, h, w, -1)[..., :self.num_classes].permute(0, 4, 1, 2, 3)}
 
     def loss(self, example, preds_dicts, **kwargs):
-        raise NotImplementedError("DeconvConvHead.loss: training the voxel segmentation head (sparse cross-entropy + Lovasz over the labelled voxels and the "
-                                  "backward of the three voxel_seg kernels) is not built; it is the follow-up of the voxel-wise head")
+        raise NotImplementedError("DeconvConvHead.loss: training the voxel segmentation head runs on the tape, at the labelled cells -- there are no dense "
+                                  "seg_preds to take a loss from; use train_voxel_seg.VoxelSegTrainStep (or train_voxel_seg.voxel_seg_loss on a tape)")
 
     def predict_panoptic(self, *args, **kwargs):
         raise NotImplementedError("DeconvConvHead.predict_panoptic: panoptic fusion on voxel predictions is not built")

@@ -110,9 +110,10 @@ def add_relu(t: ad.Tape, a: ad.Node, b: ad.Node) -> ad.Node:
 
 
 def sp_middle_resnet_fhd_train(t: ad.Tape, net: SpMiddleResNetFHD, voxel_features: torch.Tensor, coors: torch.Tensor, batch_size: int, input_shape,
-                               prefix="") -> ad.Node:
+                               prefix="", return_conv1=False):
     """-> node holding the dense NHWC BEV map (B, H', W', 128*D'); gradients of every parameter are recorded on ``t``
-    (leaf names = prefix + state-dict names)"""
+    (leaf names = prefix + state-dict names).  ``return_conv1``: -> (that node, the ``conv1`` node -- the (n, 16) rows behind stage 0's two
+    blocks, scn.py:174 -- and level 0 as an ops.SparseLevel over those rows): what the voxel segmentation head reads and sends gradients to"""
     hip.require_device(voxel_features, coors)
     lib = hip.load()
     dev, st = voxel_features.device, hip.stream()
@@ -203,6 +204,7 @@ def sp_middle_resnet_fhd_train(t: ad.Tape, net: SpMiddleResNetFHD, voxel_feature
     x = bn(x, net.conv_input[1], "conv_input.1", ops.ACT_RELU)
     for i, blk in enumerate(net.conv1):
         x = block(x, lvl, blk, f"conv1.{i}")
+    conv1, level0 = x, ops.SparseLevel(feats=x.v, index=lvl.index, keys=lvl.keys, count=lvl.count, cap=int(lvl.keys.shape[0]), dims=list(lvl.dims))
     for sname in ("conv2", "conv3", "conv4"):
         seq = getattr(net, sname)
         x, lvl = down(x, lvl, seq[0], seq[1], sname)
@@ -220,4 +222,5 @@ def sp_middle_resnet_fhd_train(t: ad.Tape, net: SpMiddleResNetFHD, voxel_feature
         hip.call("pn_sparse_from_dense_nhwc", dy.data_ptr(), last.keys.data_ptr(), last.n, last.count.data_ptr(), i4(od), cch, g.data_ptr(), st)
         ad.accumulate(xin, g, own=True)
 
-    return t.new(dense, bw)
+    out = t.new(dense, bw)
+    return (out, conv1, level0) if return_conv1 else out
