@@ -309,6 +309,40 @@ int pn_static_pfn_fwd(const float *voxels, const int32_t *num_points, const int3
                       const float *scale1, const float *shift1, int c1, float vx, float vy,
                       float x_offset, float y_offset, float *features, pn_stream_t stream);
 
+/* The same net in TRAINING form (csrc/pfn_static_train.hip): PillarFeatureNet.forward + PFNLayer.forward_static
+ * (det3d/models/readers/pillar_encoder.py:129-169, 49-61) with the module in train mode, and autograd through those lines.
+ * Per layer z = x W^T, BatchNorm1d with BATCH statistics over all V*P rows (the padded slots included; biased variance, eps),
+ * ReLU, max over the P slots; layer 1's input is [y0_p, max_p y0] for every slot.  running_mean / running_var (unbiased, n = V*P)
+ * are updated with `momentum`, num_batches_tracked (int64) goes up by 1.  c1 = 0: one layer.  V = min(*num_voxels, v_capacity) is
+ * read on the device; rows behind it are neither read nor written.  saved (2 c0 + 2 c1 floats): mean0 | rstd0 | mean1 | rstd1.
+ * Limits: p <= 32, f + 5 (+ 1) <= 16, c0 <= 64, c1 <= 128.  No atomics: every sum is taken in a fixed order.
+ * The backward takes d_features (V, c_last) or the NHWC d_canvas (B, canvas_h, canvas_w, c_last) whose rows at coors[:, (0, 2, 3)]
+ * it gathers (= the backward of PointPillarsScatter, pillar_encoder.py:199-225, fused), and writes dW0 (c0, nin), dgamma0, dbeta0
+ * and, for two layers, dW1 (c1, 2 c0), dgamma1, dbeta1 (overwritten).  The maximum's gradient goes to the first slot attaining it.
+ * Both calls share one workspace size.
+ * pn_static_pfn_train_mark_launches (measurement): the calling thread's NEXT forward or backward call records events[i] in front of
+ * its i-th launch and one more behind the last, then disarms (forward, two layers: gram, finalize0, stats1, finalize1, out = 6
+ * events; backward: gram, finalize0, finalize1, b1, finalize1, b2, finalize_b2 = 8; one layer: 4 and 5). */
+int pn_static_pfn_train_mark_launches(void **events /* pn_event_t[capacity] */, int capacity);
+size_t pn_static_pfn_train_workspace_bytes(int v_capacity, int p, int f, int with_distance, int c0, int c1);
+int pn_static_pfn_train_fwd(const float *voxels, const int32_t *num_points, const int32_t *coors,
+                            const int32_t *num_voxels, int v_capacity, int p, int f, int with_distance,
+                            const float *w0, const float *gamma0, const float *beta0, int c0, float eps0,
+                            float momentum0, float *running_mean0, float *running_var0,
+                            int64_t *num_batches_tracked0, const float *w1, const float *gamma1,
+                            const float *beta1, int c1, float eps1, float momentum1, float *running_mean1,
+                            float *running_var1, int64_t *num_batches_tracked1, float vx, float vy,
+                            float x_offset, float y_offset, float *features, float *saved, void *workspace,
+                            size_t workspace_bytes, pn_stream_t stream);
+int pn_static_pfn_train_bwd(const float *voxels, const int32_t *num_points, const int32_t *coors,
+                            const int32_t *num_voxels, int v_capacity, int p, int f, int with_distance,
+                            const float *w0, const float *gamma0, const float *beta0, int c0, const float *w1,
+                            const float *gamma1, const float *beta1, int c1, float vx, float vy,
+                            float x_offset, float y_offset, const float *saved, const float *d_features,
+                            const float *d_canvas, int canvas_h, int canvas_w, float *dw0, float *dgamma0,
+                            float *dbeta0, float *dw1, float *dgamma1, float *dbeta1, void *workspace,
+                            size_t workspace_bytes, pn_stream_t stream);
+
 /* Backward of the pillar feature net, (C0, C1) = (32, 128) or (16, 32): gradients of the two Linear weights
  * (autograd through pillar_encoder.py:393-406 / 63-71; the points are data, no gradient).
  * The incoming gradient is either d_features (V,128) or the dense canvas gradient d_canvas
@@ -1397,6 +1431,10 @@ int pn_nhwc_to_nchw_f32(const float *in, int b, int c, int h, int w, int pixel_s
 /* (B,H,W,C) -> (B,W,H,C): the (theta,r) <-> (r,theta) token order change around the attention
  * blocks, x.permute(0,1,3,2) at det3d/models/detectors/voxelnet.py:211,219 */
 int pn_transpose_hw_f32(const float *in, int b, int h, int w, int c, float *out, pn_stream_t stream);
+/* The pixel shuffle behind the GEMM form of ConvTranspose2d(kernel = stride = k, no bias), the RPN deblocks with us_layer_strides > 2
+ * (det3d/models/necks/rpn.py:80-110; us = 4 in configs/waymo/pp/*): the 1x1 product's columns (b, h, w, ky, kx, c) -> the map
+ * (b, h k, w k, c); inverse = 1: the map's gradient back to columns (the adjoint, a permutation).  c a multiple of 4. */
+int pn_depth_to_space_f32(const float *in, int b, int h, int w, int k, int c, int inverse, float *out, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Several convolutions of one tile shape as ONE launch, with the GroupNorm-family layer between two convolutions folded

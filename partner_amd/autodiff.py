@@ -523,7 +523,8 @@ def transpose_hw(t: Tape, x: Node, b: int, h: int, w: int, c: int) -> Node:
 
 
 def conv_transpose2d(t: Tape, x: Node, w: Node) -> Node:
-    """ConvTranspose2d(kernel = stride, no bias) of the RPN deblocks (rpn.py:80-110): weight (Cin, Cout, k, k), k in {1, 2}"""
+    """ConvTranspose2d(kernel = stride, no bias) of the RPN deblocks (rpn.py:80-110): weight (Cin, Cout, k, k); k = 1 and 2 on the convolution kernels,
+    any other k as a GEMM and a pixel shuffle"""
     wv = w.v
     cin, cout, k, _ = wv.shape
     if k == 1:   # a 1x1 convolution with the transposed weight
@@ -537,7 +538,27 @@ def conv_transpose2d(t: Tape, x: Node, w: Node) -> Node:
 
         return t.new(y, bw1)
     if k != 2:
-        raise hip.PartnerHipError("conv_transpose2d: only kernel = stride in {1, 2} has a HIP kernel")
+        # any other k (the Waymo pillar configs' us_layer_strides = 4): ONE GEMM to the k k Cout columns of every input pixel (ad.linear
+        # gives its data and weight gradients) and the pixel shuffle pn_depth_to_space_f32, whose adjoint is its inverse
+        if cout % 4:
+            raise hip.PartnerHipError("conv_transpose2d: kernel = stride > 2 takes an output channel count that is a multiple of 4")
+        b, h, ww, _ = x.v.shape
+        wm_v = wv.permute(2, 3, 1, 0).reshape(k * k * cout, cin).contiguous()      # row (ky k + kx) Cout + co
+
+        def wm_bw(g):      # on the stream the GEMM's weight gradient was queued on
+            side_run(lambda: accumulate(w, g.view(k, k, cout, cin).permute(3, 2, 0, 1).contiguous(), own=True), g)
+
+        wm = t.new(wm_v, wm_bw)
+        cols = linear(t, view(t, x, (b * h * ww, cin)), wm, None)
+        yk = torch.empty((b, h * k, ww * k, cout), dtype=torch.float32, device=wv.device)
+        hip.call("pn_depth_to_space_f32", cols.v.data_ptr(), b, h, ww, k, cout, 0, yk.data_ptr(), hip.stream())
+
+        def bwk(dy):
+            dcols = torch.empty_like(cols.v)
+            hip.call("pn_depth_to_space_f32", dy.contiguous().data_ptr(), b, h, ww, k, cout, 1, dcols.data_ptr(), hip.stream())
+            accumulate(cols, dcols, own=True)
+
+        return t.new(yk, bwk)
     y = ops.ConvLayer(wv, deconv2x2=True)(x.v)
 
     def bw2(dy):

@@ -385,6 +385,23 @@ __global__ void recip_clamp_bwd_kernel(const float* __restrict__ x, const float*
   if (i < n) dx[i] = x[i] > lo ? -dy[i] / (x[i] * x[i]) : 0.f;
 }
 
+// (b, h, w, k, k, c) <-> (b, h k, w k, c): the pixel shuffle behind the GEMM form of ConvTranspose2d(kernel = stride = k); i runs over
+// the float4s of the (b, h k, w k, c) map, so the wide side is always contiguous.  inverse: map -> columns
+__global__ void depth_to_space_kernel(const float* __restrict__ in, int h, int w, int k, int c4, float* __restrict__ out, size_t total4, int inverse) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
+    size_t r = i;
+    const int ch = (int)(r % c4); r /= c4;
+    const int x = (int)(r % ((size_t)w * k)); r /= (size_t)w * k;
+    const int y = (int)(r % ((size_t)h * k));
+    const size_t b = r / ((size_t)h * k);
+    const size_t col = ((((b * h + y / k) * w + x / k) * k + y % k) * k + x % k) * c4 + ch;
+    const float4* src = reinterpret_cast<const float4*>(in);
+    float4* dst = reinterpret_cast<float4*>(out);
+    if (inverse) dst[col] = src[i];
+    else dst[i] = src[col];
+  }
+}
+
 unsigned grid_for(long long total, int threads = 256) { return (unsigned)std::min<long long>(65535, (total + threads - 1) / threads); }
 
 }  // namespace
@@ -529,6 +546,13 @@ int pn_crop_roll_f32(const float* y, int batch, int h, int w, int hp, int wp, in
   PN_REQUIRE(x && y && batch >= 1 && h >= 1 && w >= 1 && hp >= h && wp >= w && c >= 1 && shift >= 0, "crop_roll: bad arguments");
   hipLaunchKernelGGL(crop_roll_kernel, dim3(grid_for((long long)batch * h * w * c)), dim3(256), 0, pn::S(stream), y, batch, h, w, hp, wp, c, shift, x);
   return pn::check_launch("crop_roll_kernel");
+}
+
+int pn_depth_to_space_f32(const float* in, int b, int h, int w, int k, int c, int inverse, float* out, pn_stream_t stream) {
+  PN_REQUIRE(in && out && in != out && b >= 1 && h >= 1 && w >= 1 && k >= 1 && c >= 4 && c % 4 == 0, "depth_to_space: bad arguments (c must be a multiple of 4)");
+  const size_t total4 = (size_t)b * h * k * w * k * (c / 4);
+  hipLaunchKernelGGL(depth_to_space_kernel, dim3(grid_for((long long)total4)), dim3(256), 0, pn::S(stream), in, h, w, k, c / 4, out, total4, inverse);
+  return pn::check_launch("depth_to_space_kernel");
 }
 
 int pn_scale_channels_f32(const float* x, const float* scale, size_t n, int c, float* y, pn_stream_t stream) {

@@ -123,6 +123,12 @@ SIGNATURES = {
     "pn_dynamic_pfn_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _I, _P, _SZ, _P]),
     "pn_dynamic_pfn_bwd_shape": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _I, _P, _P, _P, _P, _I, _P, _SZ, _P]),
     "pn_static_pfn_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _F, _F, _F, _P, _P]),
+    "pn_static_pfn_train_mark_launches": (_I, [_P, _I]),
+    "pn_static_pfn_train_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "pn_static_pfn_train_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P,
+                                     _F, _F, _F, _F, _P, _P, _P, _SZ, _P]),
+    "pn_static_pfn_train_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _I, _I,
+                                     _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "pn_scatter_canvas_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pn_fill_zero": (_I, [_P, _SZ, _P]),
     "pn_clear_canvas_cells": (_I, [_P, _P, _I, _P, _I, _P, _P]),
@@ -370,6 +376,7 @@ SIGNATURES = {
     "pn_center_loss_workspace_bytes": (_SZ, []),
     "pn_center_loss_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _F, _P, _P, _SZ, _P]),
     "pn_center_loss_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _F, _P, _F, _P, _I, _P, _P, _P]),
+    "pn_depth_to_space_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "pn_transpose_hw_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "pn_event_create": (_I, [C.POINTER(_P)]),
     "pn_event_destroy": (_I, [_P]),

@@ -364,6 +364,94 @@ def scatter_canvas(features: torch.Tensor, unq: torch.Tensor, batch: int, t: int
              canvas.data_ptr(), st)
     return canvas
 
+
+# ------------------------------------------------------------------------------ hard-voxel PillarFeatureNet, training form
+def _static_pfn_layers(layers):
+    """[(linear weight (C, K), BatchNorm1d)] of one or two PFN layers -> the pointer arguments of both entries' layer blocks"""
+    if not 1 <= len(layers) <= 2:
+        raise NotImplementedError("static_pfn_train: one or two PFN layers (csrc/pfn_static_train.hip)")
+    for w, bn in layers:
+        hip.require_device(w, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        assert w.is_contiguous() and w.dtype == torch.float32
+        if bn.momentum is None:
+            raise NotImplementedError("static_pfn_train: BatchNorm1d(momentum=None) (the cumulative average) is not built")
+    return layers[0], (layers[1] if len(layers) > 1 else (None, None))
+
+
+def static_pfn_train(voxels: torch.Tensor, num_points: torch.Tensor, coors: torch.Tensor, layers, vx: float, vy: float, x_offset: float,
+                     y_offset: float, with_distance: bool = False, num_voxels: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """``PillarFeatureNet.forward`` + ``PFNLayer.forward_static`` (pillar_encoder.py:129-169, 49-61) in TRAIN mode: BatchNorm1d batch
+    statistics over all V*P rows (the padded slots included), the running buffers and ``num_batches_tracked`` of every layer's module
+    updated in place.  voxels (V, P, F) f32, num_points (V,) int32, coors (V, 4) int32 [b, z, y, x]; ``layers``: [(linear weight,
+    BatchNorm1d module)] of one or two layers, whose parameters may be views of a flat buffer; ``num_voxels``: device count (1,) int32 -- rows
+    behind it are neither read nor written; ``out``: the feature tensor to write.  -> (features (V, C_last), saved (2 C0 + 2 C1,): mean0 | rstd0 | mean1 | rstd1 for the backward)."""
+    hip.require_device(voxels, num_points, coors)
+    assert voxels.dtype == torch.float32 and voxels.is_contiguous() and num_points.dtype == torch.int32 and coors.dtype == torch.int32
+    assert num_points.is_contiguous() and coors.is_contiguous() and coors.shape[1] == 4
+    (w0, bn0), (w1, bn1) = _static_pfn_layers(layers)
+    v, p, f = voxels.shape
+    c0, c1 = int(w0.shape[0]), (0 if w1 is None else int(w1.shape[0]))
+    dev = voxels.device
+    if num_voxels is None:
+        num_voxels = torch.full((1,), v, dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty((v, c1 or c0), dtype=torch.float32, device=dev)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (v, c1 or c0)
+    saved = torch.zeros((2 * c0 + 2 * c1,), dtype=torch.float32, device=dev)
+    nbytes = hip.load().pn_static_pfn_train_workspace_bytes(v, p, f, int(bool(with_distance)), c0, c1)
+    ws = _workspace(nbytes, dev)
+
+    def layer(w, bn):
+        if w is None:
+            return [None, None, None, 0, 0.0, 0.0, None, None, None]
+        return [w.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), int(w.shape[0]), float(bn.eps), float(bn.momentum),
+                bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()]
+
+    hip.call("pn_static_pfn_train_fwd", voxels.data_ptr(), num_points.data_ptr(), coors.data_ptr(), num_voxels.data_ptr(), v, p, f,
+             int(bool(with_distance)), *layer(w0, bn0), *layer(w1, bn1), float(vx), float(vy), float(x_offset), float(y_offset), out.data_ptr(),
+             saved.data_ptr(), ws.data_ptr(), nbytes, hip.stream())
+    return out, saved
+
+
+def static_pfn_train_bwd(voxels: torch.Tensor, num_points: torch.Tensor, coors: torch.Tensor, layers, vx: float, vy: float, x_offset: float,
+                         y_offset: float, saved: torch.Tensor, d_features: Optional[torch.Tensor] = None, d_canvas: Optional[torch.Tensor] = None,
+                         with_distance: bool = False, num_voxels: Optional[torch.Tensor] = None, out=None):
+    """the exact adjoint of ``static_pfn_train`` with respect to the parameters (the points are data).  ``d_features`` (V, C_last), or the NHWC
+    ``d_canvas`` (B, H, W, C_last) whose rows at the pillars' cells ``coors[:, (0, 2, 3)]`` are gathered in the kernel (the backward of the
+    scatter, fused).  ``layers``, ``saved`` as in the forward (the BatchNorm modules give gamma and beta).  ``out``: the gradient tensors to
+    write [dW0, dgamma0, dbeta0(, dW1, dgamma1, dbeta1)] (default: fresh ones) -> that list.  No float atomics: two calls give the same bits."""
+    hip.require_device(voxels, num_points, coors, saved)
+    assert voxels.dtype == torch.float32 and voxels.is_contiguous() and num_points.dtype == torch.int32 and coors.dtype == torch.int32
+    assert num_points.is_contiguous() and coors.is_contiguous() and coors.shape[1] == 4
+    if (d_features is None) == (d_canvas is None):
+        raise ValueError("static_pfn_train_bwd: give d_features or d_canvas, not both")
+    (w0, bn0), (w1, bn1) = _static_pfn_layers(layers)
+    v, p, f = voxels.shape
+    c0, c1 = int(w0.shape[0]), (0 if w1 is None else int(w1.shape[0]))
+    cl = c1 or c0
+    dev = voxels.device
+    h = w = 0
+    if d_features is not None:
+        hip.require_device(d_features)
+        assert d_features.dtype == torch.float32 and d_features.is_contiguous() and tuple(d_features.shape) == (v, cl)
+    else:
+        hip.require_device(d_canvas)
+        assert d_canvas.dtype == torch.float32 and d_canvas.is_contiguous() and d_canvas.dim() == 4 and d_canvas.shape[3] == cl
+        h, w = int(d_canvas.shape[1]), int(d_canvas.shape[2])
+    if num_voxels is None:
+        num_voxels = torch.full((1,), v, dtype=torch.int32, device=dev)
+    if out is None:
+        out = [torch.empty_like(t) for wt, bn in layers for t in (wt, bn.weight, bn.bias)]
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for t in out) and len(out) == 3 * len(layers)
+    nbytes = hip.load().pn_static_pfn_train_workspace_bytes(v, p, f, int(bool(with_distance)), c0, c1)
+    ws = _workspace(nbytes, dev)
+    lp = lambda wt, bn: [hip.ptr(wt), hip.ptr(None if bn is None else bn.weight), hip.ptr(None if bn is None else bn.bias)]  # noqa: E731
+    grads = [t.data_ptr() for t in out] + [None] * (6 - len(out))
+    hip.call("pn_static_pfn_train_bwd", voxels.data_ptr(), num_points.data_ptr(), coors.data_ptr(), num_voxels.data_ptr(), v, p, f,
+             int(bool(with_distance)), *lp(w0, bn0), c0, *lp(w1, bn1), c1, float(vx), float(vy), float(x_offset), float(y_offset), saved.data_ptr(),
+             hip.ptr(d_features), hip.ptr(d_canvas), h, w, *grads, ws.data_ptr(), nbytes, hip.stream())
+    return out
+
 # ------------------------------------------------------------------------------ V2 hard voxelization
 def hard_voxelize(points: torch.Tensor, voxel_size, pc_range, max_points: int, max_voxels: int):
     """-> voxels (max_voxels, max_points, F), coors int32 (max_voxels, 3) [z,theta,r], num_points int32
