@@ -1961,6 +1961,50 @@ int pn_global_augment_f32(float *points, int n, int point_stride, float *boxes, 
                           const double *translate, pn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Center-based tracking (csrc/track.hip): the greedy association of the reference's trackers on the device list, ONE launch per frame, one
+ * block per sequence, nothing read back, no host-side sizes, hipGraph-capturable, bitwise run to run (vector stores only, no atomics).
+ *
+ * pn_track_step_f32 replaces PubTracker.step_centertrack of tools/waymo_tracking/tracker.py:42-136 and tools/nusc_tracking/pub_tracker.py:
+ * 49-154 (hungarian=False) with greedy_assignment (tools/nusc_tracking/track_utils.py:3-12), the global-frame conversion in front of it
+ * (tools/waymo_tracking/test.py:172-181, transform_box) and the per-sequence reset of the drivers (test.py:103-106, pub_test.py:101-105).
+ *   in     the device list of CenterHead.predict(device_only=True): boxes (batch, capacity, box_dims = 9) f32 as (x, y, z, w, l, h, vx, vy,
+ *          rot), scores (batch, capacity) f32, label_preds (batch, capacity) int64, count (batch) int32 (clamped to 0..capacity);
+ *          pose (batch, 3, 4) f64 lidar -> tracking frame, or NULL = identity (the list is global already); time_lag (batch) f64;
+ *          first (batch) int32, nonzero = this sequence's table and id_count are reset before anything else;
+ *          track_class (num_labels) int32 = the detection label's index in the tracking name list, -1 = class not tracked (tracker.py:
+ *          50-52, :56); max_dist (num_labels) f32 (tracker.py:76); max_age; score_thresh (tracker.py:113; -inf for the nuScenes
+ *          tracker, which spawns a track for every unmatched detection, pub_tracker.py:130-136).  All pointers are device pointers.
+ *   state  one blob of pn_track_state_bytes(batch, capacity, max_age) bytes, 8-byte aligned, zero = empty, updated in place (no pointer
+ *          ping-pong: a captured graph keeps its addresses).  With T = capacity * max(1, max_age) rows per sequence -- an exact bound:
+ *          ages live in 1..max_age and each age holds at most one frame's detections -- it is, back to back, whole-batch arrays:
+ *            f64  ct (batch, T, 2) | tracking (batch, T, 2) | staging ct | staging tracking
+ *            i32  label (batch, T) | tracking_id | age | active | box_id | staging label | staging id | staging age
+ *            i32  track_count (batch) | id_count (batch)
+ *          Rows [0, track_count) are the reference's self.tracks in its order; box_id = the row of this frame's list, -1 for a coasting
+ *          track; rows past track_count that an earlier frame used hold tracking_id = age = active = 0, box_id = -1.  The staging columns are scratch of one launch.
+ *   out    tracking_ids, active (batch, capacity) int32, aligned with the list rows: 0 for a filtered class, for an unmatched row that
+ *          is not above score_thresh, and for every row at or past count.
+ *   rules  1 count == 0: the table is emptied, id_count kept (:43-45).  2 kept rows (track_class >= 0) in list order: ct = pose . (x, y, z)
+ *          and tracking = (R . (vx, vy, 0)) * -1 * time_lag in f64; query = f32(ct + f64(f32(tracking))) (:66-68).  3 distance in f32 on
+ *          the f32-rounded track ct: subtract, square, add, correctly rounded sqrt -- squared distances are never compared; a pair is
+ *          invalid when dist > max_dist[label] (equality is valid) or the classes differ (:82-89).  4 greedy, rows in list order: the
+ *          FIRST index of the minimum over valid tracks not taken yet.  5 new table = matches in row order (age 1, active = old + 1, the
+ *          track's id), then unmatched kept rows with score > score_thresh (id_count += 1, age 1, active 1), then unmatched old tracks
+ *          with age < max_age in old order (age + 1, active 0, ct += tracking * -1 in f64); the rest is dropped (:103-135).
+ *          6 THE ONE DIFFERENCE: count > 0 with every row filtered raises IndexError in the reference (results[0], :65); here the general
+ *          path runs with zero kept rows and the tracks coast.  (A NaN distance matches nothing.)
+ * PN_ERR_INVALID without a launch: null pointers (pose excepted), box_dims != 9 (no velocity, no center-based tracking: the reference
+ * itself would index out of range), num_labels outside 1..256, batch outside 1..65535, capacity outside 1..4096, max_age < 0, a state
+ * that is not 8-byte aligned, or a table the LDS layout cannot hold: T <= 8192 and 12 T + 28 capacity <= 64512 bytes (the f32 positions
+ * and classes of the old table plus five words and the query point per list row); capacity 500 with max_age 3 uses 32000.
+ * pn_track_state_bytes returns 0 for such a shape. */
+size_t pn_track_state_bytes(int batch, int capacity, int max_age);
+int pn_track_step_f32(const float *boxes, int box_dims, const float *scores, const int64_t *label_preds, const int32_t *count,
+                      const double *pose, const double *time_lag, const int32_t *first, const int32_t *track_class,
+                      const float *max_dist, int num_labels, int max_age, float score_thresh, int batch, int capacity, void *state,
+                      int32_t *tracking_ids, int32_t *active, pn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * timing helper: HIP events on `stream`, used by bench.py for the roofline object.
  */
 typedef void *pn_event_t;

@@ -264,6 +264,8 @@ SIGNATURES = {
     "pn_recip_clamp_f32": (_I, [_P, _F, _I, _P, _P]),
     "pn_recip_clamp_bwd_f32": (_I, [_P, _P, _F, _I, _P, _P]),
     "pn_global_augment_f32": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P]),
+    "pn_track_state_bytes": (_SZ, [_I, _I, _I]),
+    "pn_track_step_f32": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
     "pn_handle_create": (_I, [_I, _P]),
     "pn_handle_destroy": (_I, [_P]),
     "pn_handle_info": (_I, [_P, _P, _P, _P, _P, _P, _SZ]),
